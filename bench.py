@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the DiCoW training step on MI355X (contract: see the task description / DESIGN.md "Measurement").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: run it either under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment; WORLD_SIZE must
 equal N) or plainly -- without a rendezvous in the environment `python bench.py --gpus N` spawns the N ranks itself (one process
@@ -9,9 +9,12 @@ per GPU, LOCAL_RANK -> device, RCCL rendezvous on 127.0.0.1; what scripts/submit
 
 One "step" = forward + backward + gradient all-reduce + clip + AdamW on one synthetic batch of 30 s clips
 (whisper-large-v3-turbo dims, per-GPU batch 16, decoder frozen, L=128: BASELINE.json configs[2]/[3]); inputs are
-resident in HBM before the timed region.  Prints ONE JSON line (rank 0) with the metric, the roofline of the
-dominant kernel (live HIP-event timing of every launch of it inside the timed region) and the CPU baseline
-(the oracle timed on the host cores on a bounded sample).
+resident in HBM before the timed region.  Prints ONE JSON line (rank 0) with the metric.  A plain run sets up, warms up,
+times the K steps, writes the last timed step's outputs (--dump-outputs) and prints the line, nothing more.  --full adds
+everything else the benchmark measures after the timed region: the roofline of the dominant kernel (live HIP-event timing
+of every launch of it in instrumented steps), board power / clock during the timed region, the one-stream reference, the
+front end, the encoder forward alone, the other BASELINE.json workloads and the CPU baseline (the oracle timed on the host
+cores on a bounded sample).
 """
 import argparse
 import json
@@ -38,23 +41,23 @@ def parse():
     ap.add_argument("--ctc", action="store_true", help="recipe CTC auxiliary branch (ctc_weight 0.3, subsample, extra attention)")
     ap.add_argument("--preheat", action="store_true",
                     help="time the recipe's first phase instead (use_fddt_only_n_steps: only FDDT parameters train)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--emulate-fabric-gbps", type=float, default=0.0,
                     help="one-GPU rehearsal of the 8-rank exchange: run as rank 0 of a one-rank RCCL group with the bucketed reducer forced and, "
                          "behind every bucket's all-reduce, a 16-workgroup side-stream kernel that rewrites the bucket in place twice at this "
                          "algorithm bandwidth (GB/s) -- the CU, HBM and power load of a real ring all-reduce (dicow_fabric_emulate)")
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the other BASELINE.json workloads (configs[1] whisper-base B=8 from a hipGraph, configs[4]'s per-rank SE-DiCoW "
-                         "B=16) that the default one-GPU headline run times after its own timed region (`other_workloads` of the line)")
-    ap.add_argument("--no-power", action="store_true", help="do not sample rocm-smi (board power / shader clock) during the timed region")
+                         "B=16) that a --full one-GPU headline run times after its own timed region (`other_workloads` of the line)")
+    ap.add_argument("--no-power", action="store_true", help="--full: do not sample rocm-smi (board power / shader clock) during the timed region")
     ap.add_argument("--cpu-sample", default="turbo-b1")
     ap.add_argument("--profile-steps", type=int, default=5,
-                    help="instrumented steps run AFTER the timed region (per-launch HIP events of the dominant kernel: roofline)")
+                    help="--full: instrumented steps run AFTER the timed region (per-launch HIP events of the dominant kernel: roofline)")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured hipGraph (launch-bound configs)")
     ap.add_argument("--split-streams", action="store_true",
                     help="run each batch as two half batches on two HIP streams (trainer.SplitSync; same loss and gradients as the two halves "
                          "accumulated; measured -0.3...-1.8 ms per step, profiles/r06_split_streams.txt: not the default)")
-    ap.add_argument("--no-one-stream-ref", action="store_true", help="skip the short one-stream reference run behind the timed region")
+    ap.add_argument("--no-one-stream-ref", action="store_true", help="--full: skip the short one-stream reference run behind the timed region")
     ap.add_argument("--no-split-fwd", "--one-stream", dest="no_split_fwd", action="store_true",
                     help="the whole step on ONE stream (default: the row-parallel work of a large even batch -- encoder forward, the frozen decoder's "
                          "layers, the encoder backward's dgrad / attention / row-kernel chain -- runs as two half batches on two HIP streams into the "
@@ -72,6 +75,12 @@ def parse():
                          "gradient exchange (default 0.20 over RCCL; off in the shared-GPU gloo test mode unless given)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher self-test: rendezvous + one all-reduce per rank, no training step (runs without a GPU over gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beside the headline: roofline (instrumented steps), board power, "
+                         "one-stream reference, front end, encoder forward, other workloads, CPU baseline (the --no-* switches still apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy: its loss (float64) and a fixed, seeded sample of the "
+                         "updated trainable parameters and of their gradients (float32)")
     return ap.parse_args()
 
 
@@ -226,7 +235,7 @@ def other_workloads(legs=None):
     for name, extra in legs.items():
         t0 = time.time()
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-extra", "--no-cpu-baseline", "--no-power",
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-extra", "--no-cpu-baseline", "--no-power",
                                 "--profile-steps", "1"] + extra, capture_output=True, text=True, timeout=240,
                                env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DICOW_BENCH_CHILD")})
             line = next((ln for ln in reversed(r.stdout.splitlines()) if ln.startswith("{")), None)
@@ -240,6 +249,36 @@ def other_workloads(legs=None):
         except Exception as ex:
             out[name] = {"ms_per_step": None, "note": f"failed: {ex!r}", "wall_s": round(time.time() - t0, 1)}
     return out
+
+
+DUMP_SAMPLE = 1 << 20          # positions sampled from the trainable parameters (4 MB per float32 file)
+DUMP_SEED = 20240917
+
+
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs DIR: what the last timed step handed back and what it left in the model, for comparing two builds.
+    loss.npy: the step's loss (float64, shape [1]); params.npy / grads.npy: the updated trainable parameters and the gradients the
+    step computed, at DUMP_SAMPLE positions drawn with a fixed seed over the trainable parameters concatenated in
+    named_parameters() order (independent of the flat store's layout), float32."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    total = sum(p.numel() for _, p in named)
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    idx = torch.randint(0, total, (min(DUMP_SAMPLE, total),), generator=g).sort().values
+    params, grads, off = [], [], 0
+    for n, p in named:
+        lo, hi = torch.searchsorted(idx, torch.tensor([off, off + p.numel()])).tolist()
+        if hi > lo:
+            local = (idx[lo:hi] - off).to(p.device)
+            params.append(p.detach().reshape(-1)[local].float().cpu())
+            if p.grad is None:
+                raise RuntimeError(f"--dump-outputs: trainable parameter {n} has no gradient after the step")
+            grads.append(p.grad.detach().reshape(-1)[local].float().cpu())
+        off += p.numel()
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss)], dtype=np.float64))
+    np.save(os.path.join(out_dir, "params.npy"), torch.cat(params).numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "grads.npy"), torch.cat(grads).numpy().astype(np.float32))
 
 
 def cpu_baseline(cfg_name, labels):
@@ -613,7 +652,8 @@ def main():
     def run_step(i, **kw):
         return ts.step(front_end(i) if a.from_audio else batches[i % 2], **kw)
     timer = KernelTimer(ops, ["gemm_nt", "gemm_tn"])
-    timer.install()
+    if a.full:
+        timer.install()
 
     def sync():
         torch.cuda.synchronize()
@@ -634,7 +674,7 @@ def main():
     ts.reducer.time_exposed = True
     ts.reducer.time_buckets = world > 1 or ts.reducer.force
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
-    sampler = PowerSampler(local) if rank == 0 and not a.no_power else None
+    sampler = PowerSampler(local) if a.full and rank == 0 and not a.no_power else None
     if sampler:
         sampler.start()
     t0 = time.perf_counter()
@@ -667,61 +707,63 @@ def main():
         dt = max(float(e[0]) for e in every)
         rank_ms = [round(float(e[0]) / a.steps * 1e3, 3) for e in every]
         rank_exposed = [round(float(e[2]), 3) for e in every]
-    # ---- instrumented steps OUTSIDE the timed region: per-launch HIP events of the GEMM classes (roofline)
-    nprof = max(1, min(a.profile_steps, a.steps))
-    timer.on = True
-    split_was, ts.split_streams = ts.split_streams, False   # per-launch events of two overlapping streams would time the overlap, not the kernels
-    fwd_split_was, _engine.SPLIT_FWD = _engine.SPLIT_FWD, False      # (the same for the encoder forward's two half-batch streams)
-    for i in range(nprof):
-        run_step(i, **({"eager": True} if a.graph else {}))
-    sync()
-    timer.on = False
-    # ---- the same step on ONE stream, un-instrumented, right behind the timed region (same box, same clock state): what the two half-batch streams are worth
-    one_stream = None
-    if (fwd_split_was and not a.graph and not a.no_one_stream_ref and a.batch % 2 == 0
-            and a.batch * cfg.max_source_positions >= _engine.SPLIT_FWD_MIN_ROWS):        # (only where the two streams were in use)
-        n1 = max(2, min(6, a.steps))
-        ev1 = [torch.cuda.Event(enable_timing=True) for _ in range(n1 + 1)]
-        run_step(0)
+    if a.dump_outputs and rank == 0:                # the last timed step's outputs, before anything else runs a step
+        dump_outputs(a.dump_outputs, model, loss)
+    nprof, one_stream, fe = 0, None, None
+    if a.full:
+        # ---- instrumented steps OUTSIDE the timed region: per-launch HIP events of the GEMM classes (roofline)
+        nprof = max(1, min(a.profile_steps, a.steps))
+        timer.on = True
+        split_was, ts.split_streams = ts.split_streams, False   # per-launch events of two overlapping streams would time the overlap, not the kernels
+        fwd_split_was, _engine.SPLIT_FWD = _engine.SPLIT_FWD, False      # (the same for the encoder forward's two half-batch streams)
+        for i in range(nprof):
+            run_step(i, **({"eager": True} if a.graph else {}))
         sync()
-        ev1[0].record()
-        for i in range(n1):
-            run_step(i)
-            ev1[i + 1].record()
-        sync()
-        one_stream = {"ms_per_step": round(ev1[0].elapsed_time(ev1[n1]) / n1, 3), "steps": n1,
-                      "what": "the same step with engine.SPLIT_FWD off (forward, frozen decoder and backward chain on one stream), timed after the timed region"}
-    ts.split_streams = split_was
-    _engine.SPLIT_FWD = fwd_split_was
-    # ---- the front end by itself (HIP events on the launch stream, after the timed region): log-mel, augmentation
-    fe = None
-    if rank == 0:
-        try:
-            evs = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-            for i in range(2):
-                front_end(i)
-            t_mel = t_aug = 0.0
-            NFE = 6
-            for i in range(NFE):
-                b = dict(batches[i % 2])
-                evs[0].record()
-                b["input_features"] = log_mel(waves[i % 2], cfg.num_mel_bins)
-                evs[1].record()
-                augmenter(b)
-                evs[2].record()
-                torch.cuda.synchronize()
-                t_mel += evs[0].elapsed_time(evs[1]); t_aug += evs[1].elapsed_time(evs[2])
-            frames = N_SAMPLES // 160
-            mel_flop = a.batch * frames * (2.0 * 400 * 201 * 2 + 2.0 * 201 * cfg.num_mel_bins)
-            mel_bytes = a.batch * (N_SAMPLES * 4 + 2 * cfg.num_mel_bins * frames * 4 * 1.5)   # wave in; mel written, then read + rewritten by the normalisation pass
-            fe = {"logmel_ms": round(t_mel / NFE, 4), "logmel_gflops": round(mel_flop / (t_mel / NFE) / 1e6, 1),
-                  "logmel_algorithmic_mb": round(mel_bytes / 1e6, 1), "logmel_gbps": round(mel_bytes / (t_mel / NFE) / 1e6, 1),
-                  "augment_ms": round(t_aug / NFE, 4),
-                  "what": "dicow_logmel (the 400-point DFT as an exact-fp32 matrix product on v_mfma_f32_32x32x2_f32 + slaney mel + log / clamp) on B x 30 s of 16 kHz audio resident in HBM; "
-                          "BatchAugmenter with the STNO segment augmentation and the joint SpecAug forced on (host planner incl.)",
-                  "in_timed_region": bool(a.from_audio)}
-        except Exception as ex:
-            fe = {"logmel_ms": None, "note": f"failed: {ex!r}"}
+        timer.on = False
+        # ---- the same step on ONE stream, un-instrumented, right behind the timed region (same box, same clock state): what the two half-batch streams are worth
+        if (fwd_split_was and not a.graph and not a.no_one_stream_ref and a.batch % 2 == 0
+                and a.batch * cfg.max_source_positions >= _engine.SPLIT_FWD_MIN_ROWS):        # (only where the two streams were in use)
+            n1 = max(2, min(6, a.steps))
+            ev1 = [torch.cuda.Event(enable_timing=True) for _ in range(n1 + 1)]
+            run_step(0)
+            sync()
+            ev1[0].record()
+            for i in range(n1):
+                run_step(i)
+                ev1[i + 1].record()
+            sync()
+            one_stream = {"ms_per_step": round(ev1[0].elapsed_time(ev1[n1]) / n1, 3), "steps": n1,
+                          "what": "the same step with engine.SPLIT_FWD off (forward, frozen decoder and backward chain on one stream), timed after the timed region"}
+        ts.split_streams = split_was
+        _engine.SPLIT_FWD = fwd_split_was
+        # ---- the front end by itself (HIP events on the launch stream, after the timed region): log-mel, augmentation
+        if rank == 0:
+            try:
+                evs = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                for i in range(2):
+                    front_end(i)
+                t_mel = t_aug = 0.0
+                NFE = 6
+                for i in range(NFE):
+                    b = dict(batches[i % 2])
+                    evs[0].record()
+                    b["input_features"] = log_mel(waves[i % 2], cfg.num_mel_bins)
+                    evs[1].record()
+                    augmenter(b)
+                    evs[2].record()
+                    torch.cuda.synchronize()
+                    t_mel += evs[0].elapsed_time(evs[1]); t_aug += evs[1].elapsed_time(evs[2])
+                frames = N_SAMPLES // 160
+                mel_flop = a.batch * frames * (2.0 * 400 * 201 * 2 + 2.0 * 201 * cfg.num_mel_bins)
+                mel_bytes = a.batch * (N_SAMPLES * 4 + 2 * cfg.num_mel_bins * frames * 4 * 1.5)   # wave in; mel written, then read + rewritten by the normalisation pass
+                fe = {"logmel_ms": round(t_mel / NFE, 4), "logmel_gflops": round(mel_flop / (t_mel / NFE) / 1e6, 1),
+                      "logmel_algorithmic_mb": round(mel_bytes / 1e6, 1), "logmel_gbps": round(mel_bytes / (t_mel / NFE) / 1e6, 1),
+                      "augment_ms": round(t_aug / NFE, 4),
+                      "what": "dicow_logmel (the 400-point DFT as an exact-fp32 matrix product on v_mfma_f32_32x32x2_f32 + slaney mel + log / clamp) on B x 30 s of 16 kHz audio resident in HBM; "
+                              "BatchAugmenter with the STNO segment augmentation and the joint SpecAug forced on (host planner incl.)",
+                      "in_timed_region": bool(a.from_audio)}
+            except Exception as ex:
+                fe = {"logmel_ms": None, "note": f"failed: {ex!r}"}
     if world > 1:
         ok, sums = _replicas_agree(ts, world)
         if not ok:
@@ -738,11 +780,6 @@ def main():
         return
     ms = dt / a.steps * 1e3
     utts = a.batch * world * a.steps / dt
-    nt, tn = timer.summary("gemm_nt"), timer.summary("gemm_tn")
-    prof_ms = sum(r[0].elapsed_time(r[1]) for r in timer.rec["gemm_nt"])
-    if os.environ.get("DICOW_BENCH_BREAKDOWN"):
-        timer.breakdown("gemm_nt", nprof)
-        timer.breakdown("gemm_tn", nprof)
     peak = 2500.0
     SUSTAINED_MFMA_TF = 1845.0
     TRAFFIC = None                                   # filled in after the encoder-forward leg (the committed counter passes cover the whole command)
@@ -771,7 +808,6 @@ def main():
                    "global_batch": a.batch * world, "parallelism": f"dp{world}", "split_streams": bool(a.split_streams), "two_half_batch_streams": bool(_engine.SPLIT_FWD and a.batch % 2 == 0 and a.batch * cfg.max_source_positions >= _engine.SPLIT_FWD_MIN_ROWS and not a.graph) and {"encoder_forward": "behind the speaker-communication layers" if a.se else True, "frozen_decoder_layers": bool(_engine.SPLIT_DEC), "encoder_backward_chain": bool(_engine.SPLIT_BWD) and ("above the speaker-communication layers" if a.se else True), "weight_gradients": "one full-batch pooled launch per layer"}, "trainable_params": sum(n for q, _, n, _ in ts.store.entries if q.requires_grad)},
         "loss": float(loss),
         "per_rank_ms_per_step": rank_ms,
-        "one_stream_reference": one_stream,
         "host_enqueue_ms_per_step": round(host_s / a.steps * 1e3, 3),
         "allreduce": {"exposed_ms_per_step": rank_exposed,
                       "note": "time the compute stream waits for the side-stream RCCL buckets before the optimizer (0 at one rank)",
@@ -784,88 +820,97 @@ def main():
                       # side stream, and how long the collectives themselves kept that stream busy (GradReducer.bucket_report)
                       "buckets_per_rank": rank_buckets if any(r is not None for r in rank_buckets) else None,
                       "emulated_fabric_gbps": ts.reducer.emulate_gbps or None},
-        "roofline": {"bound": "mfma", "kernel": "gemm_ntr_kernel (persistent LDS-ring 256x256 / 192x320) / gemm_nt128t_kernel (bf16 MFMA 32x32x16; every forward Linear/conv GEMM and dgrad)",
-                     "achieved": round(nt["tflops"], 1), "peak": peak, "unit": "TFLOP/s", "frac": round(nt["tflops"] / peak, 4),
-                     "traffic": TRAFFIC, "avg_launch_ms": round(nt["avg_ms"], 4), "launches_per_step": nt["launches"] // nprof,
-                     "share_of_step": round(prof_ms / nprof / ms, 3),
-                     "measured_over": f"{nprof} instrumented steps after the timed region (HIP events around every launch, on the launch stream)",
-                     "traffic_source": TRAFFIC_SOURCE,
-                     # what the matrix pipe sustains on this board with NO memory traffic at all (tools/power_mfma.sh)
-                     "sustained_mfma_only": {"tflops": SUSTAINED_MFMA_TF, "frac_of_it": round(nt["tflops"] / SUSTAINED_MFMA_TF, 4),
-                                             "what": "register-only v_mfma_f32_32x32x16_bf16 loop on all 256 CUs, random bf16 operands, 5 s: the board "
-                                                     "settles at 1.90 GHz (constant operands: 2.39 GHz, 2453 TF); profiles/r02_power_mfma.txt"}},
-        "power": power,
-        "front_end": fe,
-        "kernels": {"gemm_tn_kernel": {"tflops": round(tn["tflops"], 1), "frac": round(tn["tflops"] / peak, 4),
-                                       "share_of_step": round(tn["total_ms"] / nprof / ms, 3),
-                                       "what": "every weight gradient incl. its split fix-up / reduce launches: gemm_tn256g_kernel (an encoder "
-                                               "layer's four dW pooled in one persistent launch) + tn_group_fixup_kernel, gemm_tn256_kernel / "
-                                               "gemm_tn_kernel + tn_reduce_kernel for the rest"}} if tn else {},
         # preheat phase: forward + dgrad only (2 x encoder + 2 x decoder), no encoder weight gradients
         "step_tflops": None if tf_utt is None else round(tf_utt * utts, 1),
     }
     out["step_mfma_frac"] = None if tf_utt is None else round(out["step_tflops"] / peak, 4)
-    # north-star headline: MFMA utilisation of the FDDT-conditioned ENCODER FORWARD alone (no activations kept), same batch
-    try:
-        T_, D_, F_, Le, Mm = cfg.max_source_positions, cfg.d_model, cfg.encoder_ffn_dim, cfg.encoder_layers, cfg.num_mel_bins
-        enc_flops = (Le * (8 * T_ * D_ * D_ + 4 * T_ * T_ * D_ + 4 * T_ * D_ * F_) + 6 * (2 * T_) * Mm * D_ + 6 * T_ * D_ * D_) * a.batch
-        b0 = batches[0]
-        kw_e = dict(stno_mask=b0["stno_mask"])
-        if a.se:
-            kw_e["enrollments"] = b0["enrollments"]
-            enc_flops = None                                   # (the SE encoder's count differs; report the time only)
-        def time_encoder(grad):
-            # grad = False: torch.no_grad(), nothing kept for a backward pass (the inference-specialised forward: the next layer's
-            # FDDT in the fc2 epilogue, no gelu' / pre-activation stores).  grad = True: the forward the TRAINING STEP runs
-            # (need_grad: FDDT + LayerNorm row kernel, gelu' saved by fc1, every activation of every layer kept until the output
-            # is dropped) -- the same launches as the forward half of a timed step, timed alone.
-            with torch.set_grad_enabled(grad):
-                for _ in range(2):
-                    o_ = model.model.encoder(b0["input_features"], **kw_e)
-                    del o_
-                torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(5):
-                    o_ = model.model.encoder(b0["input_features"], **kw_e)
-                    del o_
-                e1.record()
-                torch.cuda.synchronize()
-            return e0.elapsed_time(e1) / 5
+    if a.full:
+        nt, tn = timer.summary("gemm_nt"), timer.summary("gemm_tn")
+        prof_ms = sum(r[0].elapsed_time(r[1]) for r in timer.rec["gemm_nt"])
+        if os.environ.get("DICOW_BENCH_BREAKDOWN"):
+            timer.breakdown("gemm_nt", nprof)
+            timer.breakdown("gemm_tn", nprof)
+        out.update({
+            "one_stream_reference": one_stream,
+            "roofline": {"bound": "mfma", "kernel": "gemm_ntr_kernel (persistent LDS-ring 256x256 / 192x320) / gemm_nt128t_kernel (bf16 MFMA 32x32x16; every forward Linear/conv GEMM and dgrad)",
+                         "achieved": round(nt["tflops"], 1), "peak": peak, "unit": "TFLOP/s", "frac": round(nt["tflops"] / peak, 4),
+                         "traffic": TRAFFIC, "avg_launch_ms": round(nt["avg_ms"], 4), "launches_per_step": nt["launches"] // nprof,
+                         "share_of_step": round(prof_ms / nprof / ms, 3),
+                         "measured_over": f"{nprof} instrumented steps after the timed region (HIP events around every launch, on the launch stream)",
+                         "traffic_source": TRAFFIC_SOURCE,
+                         # what the matrix pipe sustains on this board with NO memory traffic at all (tools/power_mfma.sh)
+                         "sustained_mfma_only": {"tflops": SUSTAINED_MFMA_TF, "frac_of_it": round(nt["tflops"] / SUSTAINED_MFMA_TF, 4),
+                                                 "what": "register-only v_mfma_f32_32x32x16_bf16 loop on all 256 CUs, random bf16 operands, 5 s: the board "
+                                                         "settles at 1.90 GHz (constant operands: 2.39 GHz, 2453 TF); profiles/r02_power_mfma.txt"}},
+            "power": power,
+            "front_end": fe,
+            "kernels": {"gemm_tn_kernel": {"tflops": round(tn["tflops"], 1), "frac": round(tn["tflops"] / peak, 4),
+                                           "share_of_step": round(tn["total_ms"] / nprof / ms, 3),
+                                           "what": "every weight gradient incl. its split fix-up / reduce launches: gemm_tn256g_kernel (an encoder "
+                                                   "layer's four dW pooled in one persistent launch) + tn_group_fixup_kernel, gemm_tn256_kernel / "
+                                                   "gemm_tn_kernel + tn_reduce_kernel for the rest"}} if tn else {},
+        })
+        # north-star headline: MFMA utilisation of the FDDT-conditioned ENCODER FORWARD alone (no activations kept), same batch
+        try:
+            T_, D_, F_, Le, Mm = cfg.max_source_positions, cfg.d_model, cfg.encoder_ffn_dim, cfg.encoder_layers, cfg.num_mel_bins
+            enc_flops = (Le * (8 * T_ * D_ * D_ + 4 * T_ * T_ * D_ + 4 * T_ * D_ * F_) + 6 * (2 * T_) * Mm * D_ + 6 * T_ * D_ * D_) * a.batch
+            b0 = batches[0]
+            kw_e = dict(stno_mask=b0["stno_mask"])
+            if a.se:
+                kw_e["enrollments"] = b0["enrollments"]
+                enc_flops = None                                   # (the SE encoder's count differs; report the time only)
+            def time_encoder(grad):
+                # grad = False: torch.no_grad(), nothing kept for a backward pass (the inference-specialised forward: the next layer's
+                # FDDT in the fc2 epilogue, no gelu' / pre-activation stores).  grad = True: the forward the TRAINING STEP runs
+                # (need_grad: FDDT + LayerNorm row kernel, gelu' saved by fc1, every activation of every layer kept until the output
+                # is dropped) -- the same launches as the forward half of a timed step, timed alone.
+                with torch.set_grad_enabled(grad):
+                    for _ in range(2):
+                        o_ = model.model.encoder(b0["input_features"], **kw_e)
+                        del o_
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(5):
+                        o_ = model.model.encoder(b0["input_features"], **kw_e)
+                        del o_
+                    e1.record()
+                    torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / 5
 
-        def enc_entry(ms_, note):
-            return {"ms": round(ms_, 2), "batch": a.batch, "tflops": None if enc_flops is None else round(enc_flops / ms_ / 1e9, 1),
-                    "mfma_frac": None if enc_flops is None else round(enc_flops / ms_ / 1e9 / peak, 4), "note": note}
+            def enc_entry(ms_, note):
+                return {"ms": round(ms_, 2), "batch": a.batch, "tflops": None if enc_flops is None else round(enc_flops / ms_ / 1e9, 1),
+                        "mfma_frac": None if enc_flops is None else round(enc_flops / ms_ / 1e9 / peak, 4), "note": note}
 
-        enc_ms = time_encoder(False)
-        out["encoder_forward"] = enc_entry(enc_ms, "encoder forward only, torch.no_grad() (inference-specialised launches), algorithmic "
-                                                   "FLOPs of SURVEY 8d / dense bf16 peak 2.5 PF")
-        try:
-            assert any(p_.requires_grad for p_ in model.model.encoder.parameters())
-            out["encoder_forward_train"] = enc_entry(time_encoder(True), "encoder forward only, gradients enabled: the forward the training "
-                                                     "step runs (activations, gelu' and LayerNorm statistics saved for the backward pass)")
+            enc_ms = time_encoder(False)
+            out["encoder_forward"] = enc_entry(enc_ms, "encoder forward only, torch.no_grad() (inference-specialised launches), algorithmic "
+                                                       "FLOPs of SURVEY 8d / dense bf16 peak 2.5 PF")
+            try:
+                assert any(p_.requires_grad for p_ in model.model.encoder.parameters())
+                out["encoder_forward_train"] = enc_entry(time_encoder(True), "encoder forward only, gradients enabled: the forward the training "
+                                                         "step runs (activations, gelu' and LayerNorm statistics saved for the backward pass)")
+            except Exception as ex:
+                out["encoder_forward_train"] = {"ms": None, "note": f"failed: {ex!r}"}
         except Exception as ex:
-            out["encoder_forward_train"] = {"ms": None, "note": f"failed: {ex!r}"}
-    except Exception as ex:
-        out["encoder_forward"] = {"ms": None, "note": f"failed: {ex!r}"}
-    out["roofline"]["traffic"] = pmc_traffic(ops.gemm_dispatch_log())
-    out["roofline"]["traffic_source"] = TRAFFIC_SOURCE
-    headline = a.model.endswith("large-v3-turbo") and a.batch == 16 and not (a.se or a.ctc or a.preheat or a.graph or a.from_audio)
-    if world == 1 and headline and not a.no_extra and "DICOW_BENCH_CHILD" not in os.environ:
-        del model, ts, batches, waves                             # (the legs are processes of their own: give the memory back first)
-        import gc
-        gc.collect()
-        torch.cuda.empty_cache()
-        out["other_workloads"] = other_workloads()
-    if not a.no_cpu_baseline and world == 1:
-        try:
-            out["cpu_baseline"] = cpu_baseline(a.model, a.labels)
-        except Exception as ex:      # the bench line must still be printed
-            out["cpu_baseline"] = {"value": None, "unit": "utt/s", "cores": 0, "kind": "port", "sample": f"failed: {ex!r}"}
-        try:
-            out["cpu_baseline"]["config1"] = cpu_config1()
-        except Exception as ex:
-            out["cpu_baseline"]["config1"] = {"value": None, "sample": f"failed: {ex!r}"}
+            out["encoder_forward"] = {"ms": None, "note": f"failed: {ex!r}"}
+        out["roofline"]["traffic"] = pmc_traffic(ops.gemm_dispatch_log())
+        out["roofline"]["traffic_source"] = TRAFFIC_SOURCE
+        headline = a.model.endswith("large-v3-turbo") and a.batch == 16 and not (a.se or a.ctc or a.preheat or a.graph or a.from_audio)
+        if world == 1 and headline and not a.no_extra and "DICOW_BENCH_CHILD" not in os.environ:
+            del model, ts, batches, waves                             # (the legs are processes of their own: give the memory back first)
+            import gc
+            gc.collect()
+            torch.cuda.empty_cache()
+            out["other_workloads"] = other_workloads()
+        if not a.no_cpu_baseline and world == 1:
+            try:
+                out["cpu_baseline"] = cpu_baseline(a.model, a.labels)
+            except Exception as ex:      # the bench line must still be printed
+                out["cpu_baseline"] = {"value": None, "unit": "utt/s", "cores": 0, "kind": "port", "sample": f"failed: {ex!r}"}
+            try:
+                out["cpu_baseline"]["config1"] = cpu_config1()
+            except Exception as ex:
+                out["cpu_baseline"]["config1"] = {"value": None, "sample": f"failed: {ex!r}"}
     if dist.is_initialized():
         dist.destroy_process_group()
     if errors:

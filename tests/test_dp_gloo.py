@@ -240,3 +240,34 @@ def test_bench_preflight_over_gloo_and_the_exposed_wait_guard():
     assert msg and "30.00 ms" in msg and "20%" in msg
     topo = "x\n==== Link Type between two GPUs ====\n       GPU0         GPU1\nGPU0   0            XGMI\nGPU1   XGMI         0\n====\n"
     assert bench._link_types(topo) == {"GPU0": ["0", "XGMI"], "GPU1": ["XGMI", "0"]}
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample_of_the_step_results(tmp_path):
+    """`bench.py --dump-outputs DIR` (bench.dump_outputs): the step's loss as float64 and the same seeded positions of the trainable
+    parameters and their gradients as float32, well under 64 MB; the frozen decoder is not sampled."""
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from ts_asr_whisper_amd.trainer import freeze_by_keyword
+    m = _small_model()
+    freeze_by_keyword(m)
+    trainable = [p for p in m.parameters() if p.requires_grad]
+    for i, p in enumerate(trainable):
+        p.grad = torch.full_like(p, float(i + 1))
+    bench.dump_outputs(str(tmp_path / "a"), m, torch.tensor(2.5))
+    bench.dump_outputs(str(tmp_path / "b"), m, torch.tensor(2.5))
+    total = 0
+    for name, dtype in (("loss", np.float64), ("params", np.float32), ("grads", np.float32)):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == dtype and np.array_equal(a, b), name
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+    assert total < 64 << 20
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [2.5]
+    n = sum(p.numel() for p in trainable)
+    params, grads = np.load(tmp_path / "a" / "params.npy"), np.load(tmp_path / "a" / "grads.npy")
+    assert params.shape == grads.shape == (min(bench.DUMP_SAMPLE, n),)
+    assert set(np.unique(grads).tolist()) <= {float(i + 1) for i in range(len(trainable))}
+    flat = torch.cat([p.detach().reshape(-1) for p in trainable]).numpy()
+    assert np.isin(params, flat).all()

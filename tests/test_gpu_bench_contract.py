@@ -18,8 +18,8 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
         pytest.skip("no GPU")
     env = dict(os.environ, PYTHONPATH=ROOT)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", "whisper-tiny", "--batch", "2", "--labels", "16",
-                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT,
-                       env=env)
+                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600,
+                       cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -43,6 +43,40 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert "power" in d                                                                 # rocm-smi samples of the timed region, or None
     if d["power"] is not None:
         assert 50.0 < d["power"]["board_w_mean"] < 2000.0 and 100.0 < d["power"]["sclk_mhz_mean"] <= 2500.0 and d["power"]["samples"] >= 1
+
+
+def test_plain_bench_times_only_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) prints the headline line without the measurements that need runs of their own, honours --steps,
+    and --dump-outputs writes the last timed step's loss and its parameter / gradient sample; a second run with the same
+    arguments starts from the same inputs and dumps the same arrays."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    got = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "whisper-tiny", "--batch", "2",
+                            "--labels", "16", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        got.append(json.loads(lines[0]))
+    d = got[0]
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("higher_is_better", bool), ("dtype", str), ("ms_per_step", float)):
+        assert isinstance(d[k], t), (k, d[k])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "utt/s" and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    for k in ("roofline", "power", "one_stream_reference", "front_end", "encoder_forward", "other_workloads", "cpu_baseline"):
+        assert k not in d, k
+    total = 0
+    for name, dtype in (("loss", np.float64), ("params", np.float32), ("grads", np.float32)):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == dtype and a.shape == b.shape and np.isfinite(a).all(), name
+        assert np.array_equal(a, b), name                                        # same inputs, deterministic step
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+    assert total <= 64 << 20
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == d["loss"] == got[1]["loss"]
 
 
 def test_other_workloads_legs_report_step_time_and_throughput():

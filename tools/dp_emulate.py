@@ -17,7 +17,7 @@ def run(extra, env=None):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "DICOW_FORCE_REDUCE", "DICOW_EMULATE_FABRIC_GBPS"):
         e.pop(k, None)
     e.update(env or {})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", STEPS, "--warmup", "4", "--no-cpu-baseline", "--no-extra"] + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", STEPS, "--warmup", "4", "--full", "--no-cpu-baseline", "--no-extra"] + extra,
                        capture_output=True, text=True, env=e, cwd=ROOT)
     line = next((l for l in reversed(r.stdout.splitlines()) if l.startswith("{")), None)
     if line is None:
