@@ -436,6 +436,46 @@ int dicow_adamw_hyper(int* counters, float* hyper, const int* is_pre, int n_runs
 int dicow_adamw_f32_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, float beta1, float beta2,
                         float eps, float weight_decay, const float* gnorm_sq, float max_norm, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ multi-tensor optimizer (ABI 7, additive)
+ * torch.optim.AdamW and torch.nn.utils.clip_grad_norm_ over a LIST of separate fp32 tensors (optim.DiCoWAdamW / optim.clip_grad_norm_;
+ * reference src/models/containers.py:100-114 hands a two-group torch AdamW to the HF Trainer).  A call is described by a DEVICE table:
+ * dicow_mt_tensor[n_tensors] (four pointers, int64 element count, class index, alignment flags) and dicow_mt_chunk[n_chunks] (one
+ * per DICOW_MT_CHUNK elements of each tensor, int64 start, in table order); workgroups stride over the chunks.  The table depends on the
+ * pointers only: the host uploads it again only when they change.  Tensors of a sumsq / scale call may leave p, m, v NULL. */
+#define DICOW_MT_CHUNK 2048
+#define DICOW_MT_MAX_CLASSES 32
+#define DICOW_MT_ALIGNED_ALL 1   /* p, g, m, v all 16-byte aligned: float4 path for the adamw update */
+#define DICOW_MT_ALIGNED_G   2   /* g 16-byte aligned: float4 path for sumsq / scale */
+typedef struct {
+    float* p; float* g; float* m; float* v;
+    int64_t n;              /* elements */
+    int32_t cls;            /* class index (adamw): one class = one (param group, per-parameter step count) */
+    int32_t flags;          /* DICOW_MT_ALIGNED_* */
+} dicow_mt_tensor;          /* 48 bytes */
+typedef struct { int64_t start; int32_t tensor; int32_t len; } dicow_mt_chunk;   /* elements [start, start + len) of tensors[tensor]; 16 bytes */
+/* Per-class scalars (fp32 values of torch's double-precision host arithmetic): decay = 1 - lr wd, step_size = lr / (1 - beta1^t),
+ * bc2_sqrt = sqrt(1 - beta2^t), lerp_w = 1 - beta1, beta2, one_minus_beta2 = 1 - beta2, eps.  Passed BY VALUE as a kernel argument. */
+typedef struct {
+    float decay[DICOW_MT_MAX_CLASSES]; float step_size[DICOW_MT_MAX_CLASSES]; float bc2_sqrt[DICOW_MT_MAX_CLASSES];
+    float lerp_w[DICOW_MT_MAX_CLASSES]; float beta2[DICOW_MT_MAX_CLASSES]; float one_minus_beta2[DICOW_MT_MAX_CLASSES];
+    float eps[DICOW_MT_MAX_CLASSES];
+    int32_t n_classes;
+} dicow_mt_adamw_classes;
+int dicow_multi_chunk_elems(void);
+/* One launch over every chunk; tensors whose class lies outside [cls_base, cls_base + n_classes) are left alone (a call with more
+ * than DICOW_MT_MAX_CLASSES classes is several launches over the same table).  clip_coef: NULL, or a device float the gradients are
+ * multiplied by on the fly (g itself is not written): out[2] of dicow_multi_sumsq_f32. */
+int dicow_multi_adamw_f32(const dicow_mt_tensor* tensors, const dicow_mt_chunk* chunks, int64_t n_chunks,
+                          const dicow_mt_adamw_classes* cls, int cls_base, const float* clip_coef, void* stream);
+/* Deterministic (fixed order, no float atomics) sum of squares of every g: out[0] = sum, out[1] = sqrt(sum), out[2] = min(1, max_norm /
+ * (out[1] + 1e-6)) (NaN propagates, as in torch's clip).  ws: dicow_multi_sumsq_ws_bytes(n_chunks) bytes, 16-byte aligned, ZERO before the first
+ * call (left zero by every call); one call in flight per workspace. */
+int64_t dicow_multi_sumsq_ws_bytes(int64_t n_chunks);
+int dicow_multi_sumsq_f32(const dicow_mt_tensor* tensors, const dicow_mt_chunk* chunks, int64_t n_chunks, void* ws, int64_t ws_bytes,
+                          float* out, float max_norm, void* stream);
+/* g *= coef[0] in place, coef read from device memory (out + 2 of dicow_multi_sumsq_f32). */
+int dicow_multi_scale_f32(const dicow_mt_tensor* tensors, const dicow_mt_chunk* chunks, int64_t n_chunks, const float* coef, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------------ EXPERIMENTAL (not part of the stable ABI)
  * Declared only under -DDICOW_EXPERIMENTAL_ABI and exported only by a library built with -DDICOW_EXPERIMENTS (build.sh --exp -> libdicow_hip_exp.so).

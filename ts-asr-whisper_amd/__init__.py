@@ -11,5 +11,7 @@ from . import _lib  # noqa: F401
 from .config import DiCoWConfig, PRESETS  # noqa: F401
 from .modeling import (FDDT, DiCoWEncoder, DiCoW, DiCoWForConditionalGeneration, SpeakerCommunicationBlock,  # noqa: F401
                        shift_tokens_right, build_ts_tables)
+from .optim import DiCoWAdamW, clip_grad_norm_, dicow_optimizer  # noqa: F401
 
-__all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalGeneration", "SpeakerCommunicationBlock"]
+__all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalGeneration", "SpeakerCommunicationBlock",
+           "DiCoWAdamW", "clip_grad_norm_", "dicow_optimizer"]

@@ -91,6 +91,16 @@ class CtcPrefixArgs(C.Structure):
                 ("T", c_i), ("blank", c_i), ("eos", c_i)]
 
 
+MT_MAX_CLASSES = 32
+
+
+class MtAdamwClasses(C.Structure):
+    """dicow_mt_adamw_classes: per-class fp32 scalars of dicow_multi_adamw_f32 (passed by value to the kernel)."""
+    _fields_ = [("decay", c_f * MT_MAX_CLASSES), ("step_size", c_f * MT_MAX_CLASSES), ("bc2_sqrt", c_f * MT_MAX_CLASSES),
+                ("lerp_w", c_f * MT_MAX_CLASSES), ("beta2", c_f * MT_MAX_CLASSES), ("one_minus_beta2", c_f * MT_MAX_CLASSES),
+                ("eps", c_f * MT_MAX_CLASSES), ("n_classes", C.c_int32)]
+
+
 EPI_BIAS, EPI_GELU, EPI_RESIDUAL, EPI_OUT_F32, EPI_SCALE_N, EPI_GELU_BWD, EPI_ACCUM = 1, 2, 4, 8, 16, 32, 64
 EPI_GELU_DAUX, EPI_MUL_AUX, EPI_COLSUM, EPI_FDDT = 128, 256, 512, 1024
 EPI_LNSTAT, EPI_LNFOLD, LN_SLOTS = 2048, 4096, 16
@@ -143,6 +153,10 @@ _SIGS = {
     "dicow_adamw_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_i, c_vp, c_f, c_vp],
     "dicow_adamw_hyper": [c_vp, c_vp, c_vp, c_i, c_i, c_d, c_d, c_i, c_i, c_i, c_d, c_d, c_vp],
     "dicow_adamw_f32_dev": [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_f, c_f, c_f, c_f, c_vp, c_f, c_vp],
+    "dicow_multi_chunk_elems": [],
+    "dicow_multi_adamw_f32": [c_vp, c_vp, c_i64, C.POINTER(MtAdamwClasses), c_i, c_vp, c_vp],
+    "dicow_multi_sumsq_f32": [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_f, c_vp],
+    "dicow_multi_scale_f32": [c_vp, c_vp, c_i64, c_vp, c_vp],
 }
 
 
@@ -206,6 +220,7 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
     "dicow_logmel_ws_bytes": [c_i, c_i],
     "dicow_scb_gate_bwd_ws_bytes": [],
     "dicow_ctc_ws_bytes": [c_i, c_i, c_i],
+    "dicow_multi_sumsq_ws_bytes": [c_i64],
 }
 
 

@@ -534,3 +534,28 @@ def adamw_dev(p, g, m, v, hyper, beta1, beta2, eps, wd, gnorm_sq=None, max_norm=
     """adamw with {lr, 1 - beta1^t, 1 - beta2^t} read from the 3-float device tensor `hyper` (hipGraph replay)."""
     L.call("dicow_adamw_f32_dev", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), hyper.data_ptr(), beta1, beta2,
            eps, wd, _p(gnorm_sq), max_norm, L.stream())
+
+
+# ---- multi-tensor optimizer (dicow_multi_*; the device table is built and uploaded by optim.py)
+def multi_adamw(tensors_ptr, chunks_ptr, n_chunks, classes, cls_base=0, clip_coef=None):
+    """One launch of the multi-tensor AdamW over a device table; `classes` is an _lib.MtAdamwClasses, `clip_coef` a device float
+    (out[2:] of multi_sumsq) or None."""
+    L.check(L.lib().dicow_multi_adamw_f32(tensors_ptr, chunks_ptr, n_chunks, C.byref(classes), cls_base, _p(clip_coef), L.stream()),
+            "dicow_multi_adamw_f32")
+
+
+def multi_sumsq_ws_bytes(n_chunks) -> int:
+    return int(L.lib().dicow_multi_sumsq_ws_bytes(n_chunks))
+
+
+def multi_sumsq(tensors_ptr, chunks_ptr, n_chunks, ws, out, max_norm):
+    """out[0:3] <- (sum of squares of every g, its square root, min(1, max_norm / (norm + 1e-6))); ws: zeroed uint8 device tensor of
+    at least multi_sumsq_ws_bytes(n_chunks) bytes, one call in flight at a time."""
+    _req(out, F32, "multi_sumsq: out")
+    L.call("dicow_multi_sumsq_f32", tensors_ptr, chunks_ptr, n_chunks, ws.data_ptr(), ws.numel(), out.data_ptr(), float(max_norm),
+           L.stream())
+
+
+def multi_scale(tensors_ptr, chunks_ptr, n_chunks, coef):
+    """Every g *= coef[0] (a device float) in place."""
+    L.call("dicow_multi_scale_f32", tensors_ptr, chunks_ptr, n_chunks, coef.data_ptr(), L.stream())
