@@ -349,11 +349,15 @@ def test_graft_entry_exposes_build_and_smoke():
 
 def test_no_environment_knobs_on_the_product_dispatch_path():
     """Tuning knobs read with getenv() exist only inside `#ifdef DICOW_ABLATIONS` regions of the kernels' host code (diagnostic
-    builds of tools/build_*variants.sh); the shipped library's dispatch depends on its arguments alone."""
+    builds of tools/build_*variants.sh); the shipped library's dispatch depends on its arguments alone.  The experiment routes of
+    csrc/experiments/ are under the same rule."""
     import glob
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for path in sorted(glob.glob(os.path.join(root, "ts-asr-whisper_amd", "csrc", "*.hip")) + glob.glob(os.path.join(root, "ts-asr-whisper_amd", "csrc", "*.inc"))):
+    csrc = os.path.join(root, "ts-asr-whisper_amd", "csrc")
+    paths = [p for d in (csrc, os.path.join(csrc, "experiments")) for ext in ("*.hip", "*.inc") for p in glob.glob(os.path.join(d, ext))]
+    assert any(os.sep + "experiments" + os.sep in p for p in paths)
+    for path in sorted(paths):
         depth_abl, stack = 0, []
         for n, line in enumerate(open(path), 1):
             t = line.strip()

@@ -27,12 +27,6 @@
 #define NT_QKV_LN_FLAGS (DICOW_EPI_BIAS | DICOW_EPI_SCALE_N | DICOW_EPI_LNFOLD)
 #define NT_FC1I_LN_FLAGS (DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_LNFOLD)
 #define NT_FC1T_LN_FLAGS (DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX | DICOW_EPI_LNFOLD)
-#ifndef NT_BIG_TILES
-#define NT_BIG_TILES 200      // (see gemm_nt_impl)
-#endif
-#ifndef NT128_THREADED
-#define NT128_THREADED 3      // 0: gemm_nt_kernel<2, false>; 3: its order with descriptor addressing (shipped); 1 / 2: one barrier per step, requests threaded / in a burst (measured slower in situ)
-#endif
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void gbl_void_t;
@@ -163,13 +157,6 @@ __device__ __forceinline__ void nt_fddt_quad(float* v, const float4* w, const fl
     const f32x2g_t ol = ((tl[0] + tl[1]) + tl[2]) + tl[3], orr = ((tr[0] + tr[1]) + tr[2]) + tr[3];
     v[0] = ol.x; v[1] = ol.y; v[2] = orr.x; v[3] = orr.y;
 }
-#ifndef NTR_FDDT_DUMMY
-#define NTR_FDDT_DUMMY 0
-#endif
-__device__ __forceinline__ float rv_dummy(const float4* pr, int e, int c) {      // (row-dependent stand-in for a mask value)
-    const float4 q = pr[(e >> 2)];
-    return c == 0 ? q.x * 1e-9f : c == 1 ? q.y * 1e-9f : c == 2 ? q.z * 1e-9f : q.w * 1e-9f;
-}
 template <int FLAGS, int NQ>
 __device__ __forceinline__ void nt_epilogue_math_n(const dicow_gemm_args& a, float (&v)[4 * NQ], float (&dg)[4 * NQ], int n,
                                                    const float4& bv, const uint2* pre_aux, const float4* pre_res) {
@@ -230,22 +217,6 @@ __device__ __forceinline__ void nt_epilogue_math_n(const dicow_gemm_args& a, flo
             v[4 * u] = bf2f(f2bf(v[4 * u])) + rv.x; v[4 * u + 1] = bf2f(f2bf(v[4 * u + 1])) + rv.y;
             v[4 * u + 2] = bf2f(f2bf(v[4 * u + 2])) + rv.z; v[4 * u + 3] = bf2f(f2bf(v[4 * u + 3])) + rv.w;
         }
-#if NTR_FDDT_DUMMY
-        // timing experiment only (results wrong): the arithmetic an FDDT of the NEXT layer would add to this epilogue -- four
-        // (h w_c + b_c) m_c terms and their ordered sum per element, stand-in operands
-        {
-#pragma clang fp contract(off)
-#pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                const float h = v[e];
-                // (operands chosen so that the result stays ~h: the step's timing depends on the DATA the following GEMMs see)
-                const float w0 = 1.0f + 1e-9f * bv.x, w1 = 1.0f + 1e-9f * bv.y, w2 = 1.0f + 1e-9f * bv.z, w3 = 1.0f + 1e-9f * bv.w;
-                const float t0 = (h * w0 + 1e-9f * bv.y) * (0.25f + rv_dummy(pre_res, e, 0)), t1 = (h * w1 + 1e-9f * bv.z) * (0.25f + rv_dummy(pre_res, e, 1));
-                const float t2 = (h * w2 + 1e-9f * bv.w) * (0.25f + rv_dummy(pre_res, e, 2)), t3 = (h * w3 + 1e-9f * bv.x) * (0.25f + rv_dummy(pre_res, e, 3));
-                v[e] = ((t0 + t1) + t2) + t3;
-            }
-        }
-#endif
     }
 }
 
@@ -259,9 +230,6 @@ __device__ __forceinline__ void nt_epilogue_quad(const dicow_gemm_args& a, int r
     nt_epilogue_math<FLAGS>(a, rflags, v, dg, m, n, aux, pre_bias, pre_aux, pre_res);
     if ((flags & DICOW_EPI_GELU) && aux)
         *reinterpret_cast<uint2*>(aux + (int64_t)m * a.ldaux + n) = make_uint2(pack_bf16x2(dg[0], dg[1]), pack_bf16x2(dg[2], dg[3]));
-#ifdef NTW_NOSTORE
-    if (v[0] != 12345.678f) return;                   // diagnostic build: everything but the global stores
-#endif
     if (flags & DICOW_EPI_OUT_F32) {
         float* cp = Cf + (int64_t)m * a.ldc + n;
         if (flags & DICOW_EPI_ACCUM) {
@@ -363,7 +331,7 @@ __global__ void __launch_bounds__(256, STAGES == 2 ? 2 : 4) gemm_nt_kernel(const
 // a buffer descriptor with per-lane byte offsets computed ONCE and a scalar k offset -- no address arithmetic per step (the
 // pointer form costs two 64-bit adds per request: 16 VALU instructions per step next to 16 MFMAs).  whisper-base B = 8, whole
 // step from one hipGraph: 7.81-7.83 ms against 7.87-7.88 (tools/_c40.sh).
-// Also built (NT128_THREADED 1 / 2): ONE barrier per step, the 8 requests of stage t+1 threaded behind the first eight MFMAs of
+// Also tried (removed; the record is profiles/r06_base_kernel_table.txt): ONE barrier per step, the 8 requests of stage t+1 threaded behind the first eight MFMAs of
 // stage t, or issued in a burst behind the barrier.  In isolation (same operands over and over: L2-warm) that form is 5-12 %
 // faster on every whisper-base shape (tools/bench_base_shapes.py: fc2 47.0 -> 42.8 us, fc1 dgrad 36.4 -> 32.1); inside the step
 // it is 3 % SLOWER (8.09-8.14 ms: the kernel's 116 launches 2.93 ms against 2.68): a stage then has half a step of flight
@@ -422,21 +390,13 @@ __global__ void __launch_bounds__(256, 2) gemm_nt128t_kernel(const dicow_gemm_ar
             ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(A), 0, 0u, 0x00020000);
             rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(B), 0, 0u, 0x00020000);
         }
-#if NT128_THREADED == 3
         // old order with the cheap addressing: requests of stage t+1 first (its slot was released by the barrier that ended step
         // t-1), then wait for stage t -- a stage has a whole step of flight
 #pragma unroll
         for (int e = 0; e < 8; ++e) NT128_DMA(e, nA, kb)
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-#else
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // my share of stage t landed, my reads of stage t-1 done
-#endif
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-#if NT128_THREADED == 2
-#pragma unroll
-        for (int e = 0; e < 8; ++e) NT128_DMA(e, nA, kb)
-#endif
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
             const int c = kk * 2 + (lane >> 5);
@@ -445,29 +405,15 @@ __global__ void __launch_bounds__(256, 2) gemm_nt128t_kernel(const dicow_gemm_ar
             for (int i = 0; i < 2; ++i) wf[i] = lds_frag_nt(sB, wn * 64 + i * 32 + (lane & 31), c);
 #pragma unroll
             for (int j = 0; j < 2; ++j) xf[j] = lds_frag_nt(sA, wm * 64 + j * 32 + (lane & 31), c);
-#if NT128_THREADED == 1
-            if (kk < 2) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) NT128_DMA(kk * 4 + e, nA, kb)
-            }
-#endif
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], xf[j], acc[i][j], 0, 0, 0);
-#if NT128_THREADED == 1
-            if (kk < 2) {                             // one request behind each of this slice's four MFMAs
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
-            }
-#endif
         }
-#if NT128_THREADED == 3
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-#endif
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing (empty-descriptor) requests
 #undef NT128_DMA
@@ -737,38 +683,186 @@ extern "C" int dicow_gemm_dispatch_log(char* buf, int cap) {
     return n;
 }
 
-// ws for DICOW_EPI_COLSUM: the fused path needs 2 * ceil(M/192) partial rows (the ring kernel; 2 * ceil(M/128) only for gemm_nt2_kernel
-// of the experiments library); the fallback runs dicow_colsum_bf16 on C
-extern "C" int64_t dicow_gemm_nt_colsum_ws_bytes(int M, int N) {
-#ifdef DICOW_EXPERIMENTS
-    const int64_t fused = (int64_t)2 * dicow_cdiv(M, 128) * N * 4, fb = dicow_colsum_ws_bytes(M, N);
-#else
-    const int64_t fused = (int64_t)2 * dicow_cdiv(M, 192) * N * 4, fb = dicow_colsum_ws_bytes(M, N);
+// ------------------------------------------------------------------------------------------------ NT host dispatch
+// Thresholds of the plan (the -D overrides are for A/B builds, tools/build_var.sh):
+// 256 x 256 tiles from which the persistent ring kernel takes over from the 128 x 128 tiles (two workgroups per CU, two barriers
+// per k-step).  Below ~200 tiles the ring kernel leaves most CUs idle and its prologue / epilogue are not amortised: whisper-base
+// B = 8, whose N = 512 GEMMs are 94 tiles, measured 7.72 ms per step with the threshold at 200 and 8.01-8.03 ms at 90 or 40
+// (round 3, tools/_c32.sh)
+#ifndef NT_BIG_TILES
+#define NT_BIG_TILES 200
 #endif
-    return fused > fb ? fused : fb;
+// 128 x 128 tile count up to which the 64 x 64 deep-ring kernel takes the problem (0: never)
+#ifndef NT64_MAX_TILES128
+#define NT64_MAX_TILES128 128
+#endif
+
+// The epilogue flag sets with compile-time instantiations of the persistent kernels -- the ONE list from which the kernel attributes,
+// the launch switches and the logged kernel names are generated.  NT_EPILOGUES_COMMON(X): the eight sets of the training step, which
+// gemm_ntr_kernel has in 256 x 256 and 192 x 320 and the experiments' gemm_nt2 / gemm_ntq / gemm_ntw kernels have as well.
+// NT_EPILOGUES(BOTH, W35): all of gemm_ntr_kernel's -- BOTH(F) both tile shapes, W35(F) 192 x 320 only; -1 is the run-time-flags
+// fallback for every other set.
+#define NT_EPILOGUES_COMMON(X)                                                                                                  \
+    X(0) X(DICOW_EPI_BIAS) X(DICOW_EPI_BIAS | DICOW_EPI_SCALE_N) X(DICOW_EPI_BIAS | DICOW_EPI_GELU) X(NT_RES_FLAGS)             \
+    X(DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX) X(DICOW_EPI_MUL_AUX) X(DICOW_EPI_MUL_AUX | DICOW_EPI_COLSUM)
+#ifdef DICOW_EXPERIMENTS
+#define NT_HAS_LN_EPILOGUES 1
+#define NT_EPILOGUES_LN(BOTH, W35) W35(NT_RES_LN_FLAGS) W35(NT_FDDT_LN_FLAGS) BOTH(NT_QKV_LN_FLAGS) BOTH(NT_FC1I_LN_FLAGS) BOTH(NT_FC1T_LN_FLAGS)
+#else
+#define NT_HAS_LN_EPILOGUES 0
+#define NT_EPILOGUES_LN(BOTH, W35)
+#endif
+#define NT_EPILOGUES(BOTH, W35) BOTH(-1) NT_EPILOGUES_COMMON(BOTH) W35(NT_FDDT_FLAGS) NT_EPILOGUES_LN(BOTH, W35)
+
+static int g_ncu_all = 256;                // CUs of the device (gemm_nt_setup)
+static int nt_ncu() {                      // CUs left to the persistent kernel (dicow_set_gemm_cus)
+    const int lim = g_gemm_cus.load();
+    return (lim > 0 && lim < g_ncu_all) ? lim : g_ncu_all;
 }
 
-static int gemm_nt_impl(const dicow_gemm_args* a, void* stream, bool* fused_colsum, int* colsum_rows);
+// one-time kernel attributes (dynamic LDS sizes) and device properties; the C ABI may be entered from any host thread -- the
+// forward thread and autograd's backward thread both launch GEMMs -- so this runs under std::call_once.
+// This function is the first to name the template kernels, so its order is the order of the kernels in the code object: keep it (a
+// build with the same kernels in another order measured +0.15 % per step, profiles/r07_nt_dispatch_refactor_ab.txt).
+static void gemm_nt_setup() {
+    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS_BYTES);
+    (void)hipFuncSetAttribute((const void*)gemm_nt128t_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS_BYTES);
+    (void)hipFuncSetAttribute((const void*)gemm_nt64_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 16384);
+    (void)hipFuncSetAttribute((const void*)gemm_nt64_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 16384);
+    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS_BYTES);     // (launched by DICOW_NT_VARIANT 2 of a diagnostic build only)
+#define W35(F) (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<(F), 3, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS);
+#define BOTH(F) (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<(F), 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS); W35(F)
+    NT_EPILOGUES(BOTH, W35)
+#undef BOTH
+#undef W35
+    hipDeviceProp_t pr;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipGetDeviceProperties(&pr, dev) == hipSuccess) g_ncu_all = pr.multiProcessorCount;
+}
+
+// the FLAGS template argument that serves a flag set
+static int nt_ct_flags(int flags) {
+    switch (flags) {
+#define X(F) case (F):
+        NT_EPILOGUES(X, X)
+#undef X
+            return flags;
+        default: return -1;
+    }
+}
+static void ntr_launch(int ct_flags, bool use35, dim3 grid, hipStream_t stream, const dicow_gemm_args& a) {
+#define W35(F) case (F): hipLaunchKernelGGL((gemm_ntr_kernel<(F), 3, 5>), grid, dim3(256), NTR_LDS, stream, a); break;
+#define BOTH(F) case (F):                                                                                                       \
+        if (use35) hipLaunchKernelGGL((gemm_ntr_kernel<(F), 3, 5>), grid, dim3(256), NTR_LDS, stream, a);                       \
+        else hipLaunchKernelGGL((gemm_ntr_kernel<(F), 4, 4>), grid, dim3(256), NTR_LDS, stream, a);                             \
+        break;
+    switch (ct_flags) { NT_EPILOGUES(BOTH, W35) }
+#undef BOTH
+#undef W35
+}
+
+// ---- the plan: which kernel runs a problem, on which tiles and grid.  Host arithmetic on the arguments alone -- no launch, no
+// validation (callers that have not validated get an answer for K % 64 == 0 only) -- shared by the dispatcher and the queries of the ABI.
+enum nt_family_t {
+    NT_FAM_SKINNY,      // gemm_nt_skinny_kernel: a decoding step, M <= 16
+    NT_FAM_RING,        // gemm_ntr_kernel, persistent: use35 / grid / colsum_rows apply
+    NT_FAM_64,          // gemm_nt64_kernel<stages64>: few 128 x 128 tiles
+    NT_FAM_128T,        // gemm_nt128t_kernel
+    NT_FAM_GENERIC      // gemm_nt_kernel<2, false>: 64-bit operand offsets or a single k-step
+};
+struct nt_plan_t {
+    nt_family_t family;
+    bool off32, big;    // every operand within 32-bit byte offsets of its per-batch base; enough 256 x 256 tiles for the ring kernel
+    int grid;           // workgroups (ring: of the balanced persistent grid; others: per batch)
+    int stages64;       // NT_FAM_64: ring depth, 8 or 4
+    bool use35;         // ring: 192 x 320 tiles instead of 256 x 256
+    int colsum_rows;    // ring: partial rows a fused DICOW_EPI_COLSUM leaves in the workspace
+    int ncu;            // ring: CUs the grid was balanced for
+    bool wide_ok;       // ring: the epilogue tolerates the smaller tiles at this N
+    int64_t w35, w44;   // ring: padded area of whole rounds of `ncu` workgroups, per tile shape
+    int splitk;         // equal k ranges a deep contraction with a small output is cut into (1: none)
+};
+struct nt_knobs_t { int variant, big_tiles; };     // diagnostic builds only (experiments/gemm_nt_routes.inc); {0, NT_BIG_TILES} otherwise
 
 // ---- deep contractions with a small output (the tied LM head's dgrad: [B L, D] = d_logits [B L, 51968] . E: 32 output tiles at
 // whisper-base, 160 at large-v3-turbo, 812 k-steps each): the contraction is cut into S equal ranges that run as the S
 // "batches" of one launch (operand stride = the range's k offset) writing fp32 partials to the caller's workspace; one small
 // kernel adds them in range order and rounds once.  Deterministic; only taken when the caller provides the workspace.
-static int g_ncu_all = 256;
-static int nt_splitk_plan(const dicow_gemm_args* a) {
-    if (a->batch > 1 || (a->flags & ~DICOW_EPI_OUT_F32) != 0 || a->bias || a->residual || a->aux) return 1;
-    if (a->K % BK != 0 || a->K < 8192 || a->M <= 16) return 1;
-    const int64_t tiles = (int64_t)dicow_cdiv(a->M, BM) * dicow_cdiv(a->N, BN);
-    if (tiles >= 2 * g_ncu_all) return 1;                      // enough tiles already (two 128 x 128 workgroups per CU)
-    const int nk = a->K / BK;
+static int nt_splitk_count(const dicow_gemm_args& a, int64_t tiles128) {
+    if (a.batch > 1 || (a.flags & ~DICOW_EPI_OUT_F32) != 0 || a.bias || a.residual || a.aux) return 1;
+    if (a.K % BK != 0 || a.K < 8192 || a.M <= 16) return 1;
+    if (tiles128 >= 2 * g_ncu_all) return 1;                   // enough tiles already (two 128 x 128 workgroups per CU)
+    const int nk = a.K / BK;
     int best = 1;
     for (int sp = 2; sp <= 64; ++sp) {
         if (nk % sp != 0 || nk / sp < 16) continue;            // equal ranges of at least 1024 columns
         best = sp;
-        if (tiles * sp >= 2 * g_ncu_all) break;                // the first divisor that fills every workgroup slot
+        if (tiles128 * sp >= 2 * g_ncu_all) break;             // the first divisor that fills every workgroup slot
     }
     return best;
 }
+
+static nt_plan_t nt_plan(const dicow_gemm_args& a, int ncu, int variant = 0, int big_tiles = NT_BIG_TILES) {
+    nt_plan_t p = {};
+    const int batch = a.batch > 0 ? a.batch : 1;
+    const int64_t tiles128 = (int64_t)dicow_cdiv(a.M, BM) * dicow_cdiv(a.N, BN);
+    p.splitk = nt_splitk_count(a, tiles128);
+    // the persistent kernel wins once it can put ~one workgroup on every CU; smaller problems keep the 128x128 tiles.
+    // It addresses its operands with 32-bit byte offsets from a per-batch base and needs at least two 64-deep k-steps
+    const bool ab32 = (int64_t)a.M * a.lda * 2 < (1ll << 31) && (int64_t)a.N * a.ldb * 2 < (1ll << 31);
+    p.off32 = ab32 && (int64_t)a.M * a.ldc * 4 < (1ll << 31) && (int64_t)a.M * a.ldaux * 2 < (1ll << 31) &&
+              (int64_t)a.M * a.ldr * 4 < (1ll << 31);
+    const int64_t t44 = (int64_t)dicow_cdiv(a.M, 256) * dicow_cdiv(a.N, 256) * batch;
+    p.big = p.off32 && a.K >= 2 * BK && t44 >= big_tiles;
+    if (a.M <= 16 && batch == 1 && variant == 0) {        // a decoding step: stream the weights once
+        p.family = NT_FAM_SKINNY;
+        p.grid = dicow_cdiv(a.N, 16);
+        return p;
+    }
+    if ((variant >= 4 || (variant == 0 && p.big)) && a.M >= 256 && a.N >= 256) {
+        p.family = NT_FAM_RING;
+        p.ncu = ncu;
+        // tile shape: 192x320 where its whole rounds of `ncu` workgroups pad the problem less than 256x256 does AND the
+        // output is narrow (M = 24000: the N = 1280 shapes gain 2-5 %; N = 3840 is neutral and N = 5120 with the GELU
+        // epilogue loses -- more, smaller tiles mean more epilogues).  Diagnostic builds: DICOW_NT_VARIANT 21 / 22 force the
+        // ring kernel's 256x256 / 192x320 tiles, 12 / 13 the two-stage kernel's
+        const int64_t t35 = (int64_t)dicow_cdiv(a.M, 192) * dicow_cdiv(a.N, 320) * batch;
+        p.w44 = dicow_cdiv(t44, ncu) * 256 * 256;
+        p.w35 = dicow_cdiv(t35, ncu) * 192 * 320;
+        // (round 3: with the cheaper GELU the inference fc1 -- bias + GELU, no saved derivative -- gains 8 us per launch from
+        // the smaller tiles at N = 5120 too: encoder forward 38.86 -> 38.60 ms in-situ; the training epilogues still lose)
+        p.wide_ok = a.N <= 2048 || a.flags == (DICOW_EPI_BIAS | DICOW_EPI_GELU) || a.flags == NT_FC1I_LN_FLAGS;
+        // (only the 192 x 320 instantiations carry the FDDT and LNSTAT epilogues)
+        const bool fddt = (a.flags & DICOW_EPI_FDDT) != 0, lnstat = (a.flags & DICOW_EPI_LNSTAT) != 0;
+        // (round 6, interleaved A/B of the tile choice per epilogue kind -- profiles/r06_epilogues.txt: the choices above hold, except that a
+        // PLAIN product (no epilogue work at all: the dgrads of out-proj / qkv / fc1) is 1.7-2.1 % faster on 256 x 256 at N = 1280 too)
+        const bool plain256 = a.flags == 0;
+        p.use35 = fddt || lnstat || variant == 13 || variant == 22 ||
+                  (variant != 12 && variant != 21 && a.N >= 320 && p.wide_ok && !plain256 && p.w35 < p.w44);
+        const int total = (int)(p.use35 ? t35 : t44);
+        // balanced grid: with r = ceil(total / ncu) rounds needed anyway, ceil(total / r) workgroups each take r (or
+        // r - 1) tiles -- e.g. 470 tiles run on 235 workgroups x 2 instead of 214 x 2 + 42 x 1: same makespan, fewer
+        // CUs competing for L2 / HBM / power while the last round is partial (measured 0.304 -> 0.287 ms)
+        p.grid = dicow_cdiv(total, dicow_cdiv(total, ncu));
+        p.colsum_rows = 2 * dicow_cdiv(a.M, p.use35 ? 192 : 256);
+        return p;
+    }
+    // few 128 x 128 tiles (the decoder at training time: M = batch x label length): 64 x 64 tiles on a deep ring; otherwise the
+    // descriptor-addressed 128 x 128 kernel where one batch slice of A / B fits 32-bit byte offsets and K has two k-steps
+    const bool t128 = ab32 && a.K >= 2 * BK;
+    if (NT64_MAX_TILES128 > 0 && t128 && variant == 0 && tiles128 * batch <= NT64_MAX_TILES128) {
+        p.family = NT_FAM_64;
+        p.grid = dicow_cdiv(a.M, 64) * dicow_cdiv(a.N, 64);
+        p.stages64 = (int64_t)p.grid * batch <= g_ncu_all ? 8 : 4;       // one workgroup per CU anyway: the whole 128 KiB ring
+    } else {
+        p.family = t128 ? NT_FAM_128T : NT_FAM_GENERIC;
+        p.grid = (int)tiles128;
+    }
+    return p;
+}
+
+static int nt_splitk_plan(const dicow_gemm_args* a) { return nt_plan(*a, nt_ncu()).splitk; }
 extern "C" int64_t dicow_gemm_nt_splitk_ws_bytes(const dicow_gemm_args* a) {
     if (!a) return 0;
     const int sp = nt_splitk_plan(a);
@@ -788,23 +882,27 @@ __global__ void nt_splitk_reduce_kernel(const float* __restrict__ ws, int splits
     }
 }
 
+// ws for DICOW_EPI_COLSUM: the fused path needs 2 * ceil(M/192) partial rows (the ring kernel; 2 * ceil(M/128) for gemm_nt2_kernel
+// wherever that kernel is compiled in); the fallback runs dicow_colsum_bf16 on C
+extern "C" int64_t dicow_gemm_nt_colsum_ws_bytes(int M, int N) {
+    const int64_t fused = (int64_t)2 * dicow_cdiv(M, NT_EXPERIMENT_KERNELS ? 128 : 192) * N * 4, fb = dicow_colsum_ws_bytes(M, N);
+    return fused > fb ? fused : fb;
+}
+
 extern "C" int dicow_gemm_nt_is_persistent(const dicow_gemm_args* a) {
-    if (!a || a->M < 256 || a->N < 256 || a->K < 2 * BK || a->K % BK != 0) return 0;
-    const int batch = a->batch > 0 ? a->batch : 1;
-    const bool off32 = (int64_t)a->M * a->lda * 2 < (1ll << 31) && (int64_t)a->N * a->ldb * 2 < (1ll << 31) &&
-                       (int64_t)a->M * a->ldc * 4 < (1ll << 31) && (int64_t)a->M * a->ldaux * 2 < (1ll << 31) &&
-                       (int64_t)a->M * a->ldr * 4 < (1ll << 31);
-    return (off32 && (int64_t)dicow_cdiv(a->M, 256) * dicow_cdiv(a->N, 256) * batch >= NT_BIG_TILES) ? 1 : 0;
+    return (a && a->K % BK == 0 && nt_plan(*a, nt_ncu()).family == NT_FAM_RING) ? 1 : 0;
 }
 
 #ifdef DICOW_EXPERIMENTS
 extern "C" int dicow_gemm_nt_lnstat_ok(const dicow_gemm_args* a) {
-    // (the LNSTAT instantiations are 192 x 320 only and the dispatcher forces that shape for them: what remains to ask is whether
+    // (the LNSTAT instantiations are 192 x 320 only and the plan forces that shape for them: what remains to ask is whether
     // the problem reaches the persistent kernel at all and whether its columns are whole 320-wide tiles that fit the 16 slots)
     return (dicow_gemm_nt_is_persistent(a) && a->M >= 256 && a->N >= 320 && a->N % 320 == 0 && a->N <= 1280 &&
             (int64_t)a->M * 128 < (1ll << 31) && (a->batch <= 1)) ? 1 : 0;
 }
 #endif
+
+static int gemm_nt_impl(const dicow_gemm_args* a, void* stream, bool* fused_colsum, int* colsum_rows);
 
 extern "C" int dicow_gemm_nt(const dicow_gemm_args* a, void* stream) {
     DICOW_REQUIRE(a && a->A && a->B && a->C, "gemm_nt: null operand");
@@ -839,110 +937,21 @@ extern "C" int dicow_gemm_nt(const dicow_gemm_args* a, void* stream) {
     return dicow_colsum_bf16(a->C, a->ldc, a->colsum_out, a->M, a->N, a->colsum_ws, a->colsum_ws_bytes, stream);
 }
 
-// one-time kernel attributes (dynamic LDS sizes) and device properties; the C ABI may be entered from any host thread -- the
-// forward thread and autograd's backward thread both launch GEMMs -- so this runs under std::call_once
-static void gemm_nt_setup() {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_nt128t_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS_BYTES);
-#if NT128W
-    (void)hipFuncSetAttribute((const void*)gemm_nt128w_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NT128W_LDS);
-#endif
-    (void)hipFuncSetAttribute((const void*)gemm_nt64_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 16384);
-    (void)hipFuncSetAttribute((const void*)gemm_nt64_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 16384);
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NT_LDS_BYTES);
-#define NTR_ATTR(F) (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<F, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS); \
-                    (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<F, 3, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS)
-    NTR_ATTR(-1); NTR_ATTR(0); NTR_ATTR(DICOW_EPI_BIAS); NTR_ATTR(DICOW_EPI_BIAS | DICOW_EPI_SCALE_N);
-    NTR_ATTR(DICOW_EPI_BIAS | DICOW_EPI_GELU); NTR_ATTR(DICOW_EPI_BIAS | DICOW_EPI_RESIDUAL | DICOW_EPI_OUT_F32);
-    NTR_ATTR(DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX); NTR_ATTR(DICOW_EPI_MUL_AUX);
-    NTR_ATTR(DICOW_EPI_MUL_AUX | DICOW_EPI_COLSUM);
-#undef NTR_ATTR
-#if NT_EXPERIMENT_KERNELS
-#define NT2_ATTR(F) (void)hipFuncSetAttribute((const void*)gemm_nt2_kernel<F>, hipFuncAttributeMaxDynamicSharedMemorySize, NT2_LDS)
-    NT2_ATTR(0); NT2_ATTR(DICOW_EPI_BIAS); NT2_ATTR(DICOW_EPI_BIAS | DICOW_EPI_SCALE_N); NT2_ATTR(DICOW_EPI_BIAS | DICOW_EPI_GELU);
-    NT2_ATTR(DICOW_EPI_BIAS | DICOW_EPI_RESIDUAL | DICOW_EPI_OUT_F32); NT2_ATTR(DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX);
-    NT2_ATTR(DICOW_EPI_MUL_AUX); NT2_ATTR(DICOW_EPI_MUL_AUX | DICOW_EPI_COLSUM);
-#undef NT2_ATTR
-#define NTQ_ATTR(F) (void)hipFuncSetAttribute((const void*)gemm_ntq_kernel<F>, hipFuncAttributeMaxDynamicSharedMemorySize, NTQ_LDS)
-    NTQ_ATTR(0); NTQ_ATTR(DICOW_EPI_BIAS); NTQ_ATTR(DICOW_EPI_BIAS | DICOW_EPI_SCALE_N); NTQ_ATTR(DICOW_EPI_BIAS | DICOW_EPI_GELU);
-    NTQ_ATTR(DICOW_EPI_BIAS | DICOW_EPI_RESIDUAL | DICOW_EPI_OUT_F32); NTQ_ATTR(DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX);
-    NTQ_ATTR(DICOW_EPI_MUL_AUX); NTQ_ATTR(DICOW_EPI_MUL_AUX | DICOW_EPI_COLSUM);
-#undef NTQ_ATTR
-#endif
-    (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<NT_FDDT_FLAGS, 3, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS);
-#ifdef DICOW_EXPERIMENTS
-    (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<NT_RES_LN_FLAGS, 3, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<NT_FDDT_LN_FLAGS, 3, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<NT_QKV_LN_FLAGS, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<NT_QKV_LN_FLAGS, 3, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<NT_FC1I_LN_FLAGS, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<NT_FC1I_LN_FLAGS, 3, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<NT_FC1T_LN_FLAGS, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<NT_FC1T_LN_FLAGS, 3, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, NTR_LDS);
-#endif
-#ifdef DICOW_ABLATIONS
-    (void)hipFuncSetAttribute((const void*)gemm_nt256s_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NTS_LDS);
-#define NTW_ATTR(F) (void)hipFuncSetAttribute((const void*)gemm_ntw_kernel<F, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, NTW_LDS); \
-                    (void)hipFuncSetAttribute((const void*)gemm_ntw_kernel<F, 3, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, NTW_LDS)
-    NTW_ATTR(-1); NTW_ATTR(0); NTW_ATTR(DICOW_EPI_BIAS); NTW_ATTR(DICOW_EPI_BIAS | DICOW_EPI_SCALE_N);
-    NTW_ATTR(DICOW_EPI_BIAS | DICOW_EPI_GELU); NTW_ATTR(DICOW_EPI_BIAS | DICOW_EPI_RESIDUAL | DICOW_EPI_OUT_F32);
-    NTW_ATTR(DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX); NTW_ATTR(DICOW_EPI_MUL_AUX);
-    NTW_ATTR(DICOW_EPI_MUL_AUX | DICOW_EPI_COLSUM);
-#undef NTW_ATTR
-    (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, NT256_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, NT256_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, NT256_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, NT256_LDS);
-    (void)hipFuncSetAttribute((const void*)gemm_nt256_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, NT256_LDS);
-#endif
-    hipDeviceProp_t pr;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipGetDeviceProperties(&pr, dev) == hipSuccess) g_ncu_all = pr.multiProcessorCount;
+// the fused column sums exist in the persistent kernels' MUL_AUX epilogue only: `flags` arrive without COLSUM and get it back here
+static inline void nt_fuse_colsum(dicow_gemm_args* a, bool want_colsum, bool* fused_colsum) {
+    if (want_colsum && a->flags == DICOW_EPI_MUL_AUX) { a->flags |= DICOW_EPI_COLSUM; *fused_colsum = true; }
 }
 
-// 256 x 256 tiles from which the persistent ring kernel takes over from the 128 x 128 tiles (two workgroups per CU, two barriers
-// per k-step).  Below ~200 tiles the ring kernel leaves most CUs idle and its prologue / epilogue are not amortised: whisper-base
-// B = 8, whose N = 512 GEMMs are 94 tiles, measured 7.72 ms per step with the threshold at 200 and 8.01-8.03 ms at 90 or 40
-// (round 3, tools/_c32.sh)
-// 128 x 128 tile count up to which the 64 x 64 deep-ring kernel takes the problem (0: never)
-#ifndef NT64_MAX_TILES128
-#define NT64_MAX_TILES128 128
+// ---- the hook of the experiments: kernels and DICOW_NT_VARIANT routes of diagnostic builds live in csrc/experiments/
+#define NT_NOT_ROUTED 1
+#if NT_EXPERIMENT_KERNELS || NT128W
+#include "experiments/gemm_nt_routes.inc"
+#else
+static inline nt_knobs_t nt_experiment_knobs() { return {0, NT_BIG_TILES}; }
+static inline int nt_experiment_route(dicow_gemm_args*, const nt_plan_t&, int, bool, bool*, int*, hipStream_t) { return NT_NOT_ROUTED; }
 #endif
-#ifndef NT64_SMALLK
-#define NT64_SMALLK 0             // ... and problems of up to NT64_SMALLK_TILES128 tiles whose contraction is this short (latency-bound walks)
-#endif
-#ifndef NT64_SMALLK_TILES128
-#define NT64_SMALLK_TILES128 1024
-#endif
-#ifndef NT64_DEEP_ALWAYS
-#define NT64_DEEP_ALWAYS 0
-#endif
-#ifndef NT_WIDE35
-#define NT_WIDE35 0
-#endif
-#ifndef NT_BIG_TILES
-#define NT_BIG_TILES 200
-#endif
-#ifndef NT128W_MIN_TILES
-#define NT128W_MIN_TILES 96
-#endif
-#ifndef NT_DEFER
-#define NT_DEFER 0                // experiment (tools/build_ntd.sh): bit 0 inference fc1 (bias + GELU), bit 1 training fc1 on gemm_ntd_kernel
-#endif
-#ifndef NT_DEFER_BUILD
-#define NT_DEFER_BUILD 0
-#endif
-#if NT_DEFER_BUILD
-extern "C" int dicow_ntd_launch_(const dicow_gemm_args* a, int grid, void* stream);      // experiments/gemm_ntd.hip (internal)
-extern "C" int dicow_ntd_mode_(int dflt);
-extern "C" int dicow_ntl_launch_(const dicow_gemm_args* a, int grid, void* stream);      // experiments/gemm_ntl.hip (internal)
-#endif
-static int gemm_nt_impl(const dicow_gemm_args* a_in, void* stream, bool* fused_colsum, int* colsum_rows) {
-    dicow_gemm_args a_copy = *a_in;
-    dicow_gemm_args* a = &a_copy;
-    const bool want_colsum = (a->flags & DICOW_EPI_COLSUM) != 0;
-    a->flags &= ~DICOW_EPI_COLSUM;                    // put back below where the fused epilogue exists
+
+static int nt_check_args(const dicow_gemm_args* a) {
     DICOW_REQUIRE(a && a->A && a->B && a->C, "gemm_nt: null operand");
     DICOW_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0, "gemm_nt: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
     DICOW_REQUIRE(a->K % BK == 0, "gemm_nt: K=%d must be a multiple of %d (pad the operands)", a->K, BK);
@@ -956,266 +965,78 @@ static int gemm_nt_impl(const dicow_gemm_args* a_in, void* stream, bool* fused_c
     DICOW_REQUIRE(!(a->flags & DICOW_EPI_GELU_DAUX) || ((a->flags & DICOW_EPI_GELU) && a->aux), "gemm_nt: GELU_DAUX needs GELU and aux");
     DICOW_REQUIRE(!(a->aux) || a->ldaux % 4 == 0, "gemm_nt: ldaux must be a multiple of 4");
     DICOW_REQUIRE(!(a->flags & DICOW_EPI_SCALE_N) || a->scale_ncols % 4 == 0, "gemm_nt: SCALE_N works on column quads, scale_ncols=%d", a->scale_ncols);
+    return DICOW_OK;
+}
+// the epilogues that only the persistent kernel implements (FDDT, and the LayerNorm fold of the experiments library), against the plan
+static int nt_check_ring_epilogues(const dicow_gemm_args* a, const nt_plan_t& p, int variant) {
     const int batch = a->batch > 0 ? a->batch : 1;
-    const int ntm = dicow_cdiv(a->M, BM), ntn = dicow_cdiv(a->N, BN);
+    const bool ring = variant == 0 && p.big && a->M >= 256 && a->N >= 320;
+    DICOW_REQUIRE(NT_HAS_LN_EPILOGUES || !(a->flags & (DICOW_EPI_LNSTAT | DICOW_EPI_LNFOLD)), "gemm_nt: EPI_LNSTAT / EPI_LNFOLD are experimental (the LayerNorm fold measured slower, profiles/r04_lnfold.txt): build.sh --exp builds libdicow_hip_exp.so, which has them");
+    DICOW_REQUIRE(!(a->flags & (DICOW_EPI_LNSTAT | DICOW_EPI_LNFOLD)) || ring,
+                  "gemm_nt: EPI_LNSTAT / EPI_LNFOLD are implemented by the persistent kernel only (M=%d N=%d K=%d: ask dicow_gemm_nt_is_persistent / dicow_gemm_nt_lnstat_ok)", a->M, a->N, a->K);
+    DICOW_REQUIRE(!(a->flags & DICOW_EPI_FDDT) || ring,
+                  "gemm_nt: EPI_FDDT is implemented by the persistent kernel only (M=%d N=%d K=%d is below its threshold: ask dicow_gemm_nt_is_persistent)", a->M, a->N, a->K);
+    const bool fddt = (a->flags & DICOW_EPI_FDDT) != 0, lnstat = (a->flags & DICOW_EPI_LNSTAT) != 0, lnfold = (a->flags & DICOW_EPI_LNFOLD) != 0;
+    DICOW_REQUIRE(!fddt || ((a->flags == NT_FDDT_FLAGS || a->flags == NT_FDDT_LN_FLAGS) && variant == 0 && a->N >= 320 && batch == 1 && a->fddt_rowmask &&
+                            a->fddt_w[0] && a->fddt_w[1] && a->fddt_w[2] && a->fddt_w[3] && a->fddt_b[0] && a->fddt_b[1] &&
+                            a->fddt_b[2] && a->fddt_b[3]),
+                  "gemm_nt: EPI_FDDT needs BIAS | RESIDUAL | OUT_F32, N >= 320, one batch, the eight vectors and the row masks");
+    DICOW_REQUIRE(!lnstat || ((a->flags == NT_RES_LN_FLAGS || a->flags == NT_FDDT_LN_FLAGS) && variant == 0 && batch == 1 && a->aux &&
+                              a->lnstat && a->N % 320 == 0 && a->N <= 1280 && (int64_t)a->M * 128 < (1ll << 31)),
+                  "gemm_nt: EPI_LNSTAT needs BIAS | RESIDUAL | OUT_F32 [| FDDT], aux (the bf16 copy), lnstat, N %% 320 == 0, N <= 1280 (N=%d)", a->N);
+    DICOW_REQUIRE(!lnfold || ((a->flags == NT_QKV_LN_FLAGS || a->flags == NT_FC1I_LN_FLAGS || a->flags == NT_FC1T_LN_FLAGS) && variant == 0 &&
+                              batch == 1 && a->lnstat && a->ln_c && a->bias && a->ln_nslots > 0 && a->ln_nslots <= DICOW_LN_SLOTS &&
+                              a->ln_nslots % 4 == 0 && a->ln_inv_dim > 0.f && (int64_t)a->M * 128 < (1ll << 31)),
+                  "gemm_nt: EPI_LNFOLD needs BIAS with SCALE_N or GELU [| GELU_DAUX], lnstat, ln_c, ln_nslots (multiple of 4, <= 16), ln_inv_dim");
+    return DICOW_OK;
+}
+
+static int gemm_nt_impl(const dicow_gemm_args* a_in, void* stream_, bool* fused_colsum, int* colsum_rows) {
+    dicow_gemm_args a_copy = *a_in;
+    dicow_gemm_args* a = &a_copy;
+    const hipStream_t stream = (hipStream_t)stream_;
+    const bool want_colsum = (a->flags & DICOW_EPI_COLSUM) != 0;
+    a->flags &= ~DICOW_EPI_COLSUM;                    // put back where the fused epilogue exists (nt_fuse_colsum)
+    int rc = nt_check_args(a);
+    if (rc != DICOW_OK) return rc;
     static std::once_flag once;
     std::call_once(once, gemm_nt_setup);
-#ifdef DICOW_ABLATIONS
-    const char* variant_ev = getenv("DICOW_NT_VARIANT");                   // diagnostic builds only; read per call so that a tool can
-    const int variant = variant_ev ? atoi(variant_ev) : 0;                 // interleave tile shapes in one process (tools/ab_epilogues.py)
-#else
-    constexpr int variant = 0;
-#endif
-    if (a->M <= 16 && batch == 1 && variant == 0) {       // a decoding step: stream the weights once (gemm_nt_skinny_kernel)
-        hipLaunchKernelGGL(gemm_nt_skinny_kernel, dim3(dicow_cdiv(a->N, 16)), dim3(256), 0, (hipStream_t)stream, *a);
+    const nt_knobs_t knobs = nt_experiment_knobs();
+    const nt_plan_t p = nt_plan(*a, nt_ncu(), knobs.variant, knobs.big_tiles);
+    const dim3 grid(p.grid, 1, a->batch > 0 ? a->batch : 1);
+    if (p.family == NT_FAM_SKINNY) {
+        hipLaunchKernelGGL(gemm_nt_skinny_kernel, grid, dim3(256), 0, stream, *a);
         DICOW_CHECK_LAUNCH("gemm_nt_skinny_kernel");
         if (fused_colsum) *fused_colsum = false;
         return DICOW_OK;
     }
-    // the persistent kernel wins once it can put ~one workgroup on every CU; smaller problems keep the 128x128 tiles.
-    // It addresses its operands with 32-bit byte offsets from a per-batch base and needs at least two 64-deep k-steps
-    const bool off32 = (int64_t)a->M * a->lda * 2 < (1ll << 31) && (int64_t)a->N * a->ldb * 2 < (1ll << 31) &&
-                       (int64_t)a->M * a->ldc * 4 < (1ll << 31) && (int64_t)a->M * a->ldaux * 2 < (1ll << 31) &&
-                       (int64_t)a->M * a->ldr * 4 < (1ll << 31);
-#ifdef DICOW_ABLATIONS
-    static const int big_tiles = getenv("DICOW_NT_BIG") ? atoi(getenv("DICOW_NT_BIG")) : NT_BIG_TILES;
-#else
-    constexpr int big_tiles = NT_BIG_TILES;
-#endif
-    const bool big = off32 && a->K >= 2 * BK && (int64_t)dicow_cdiv(a->M, 256) * dicow_cdiv(a->N, 256) * batch >= big_tiles;
-#ifndef DICOW_EXPERIMENTS
-    DICOW_REQUIRE(!(a->flags & (DICOW_EPI_LNSTAT | DICOW_EPI_LNFOLD)), "gemm_nt: EPI_LNSTAT / EPI_LNFOLD are experimental (the LayerNorm fold measured slower, profiles/r04_lnfold.txt): build.sh --exp builds libdicow_hip_exp.so, which has them");
-#endif
-    DICOW_REQUIRE(!(a->flags & (DICOW_EPI_LNSTAT | DICOW_EPI_LNFOLD)) || (variant == 0 && big && a->M >= 256 && a->N >= 320),
-                  "gemm_nt: EPI_LNSTAT / EPI_LNFOLD are implemented by the persistent kernel only (M=%d N=%d K=%d: ask dicow_gemm_nt_is_persistent / dicow_gemm_nt_lnstat_ok)", a->M, a->N, a->K);
-    DICOW_REQUIRE(!(a->flags & DICOW_EPI_FDDT) || (variant == 0 && big && a->M >= 256 && a->N >= 320),
-                  "gemm_nt: EPI_FDDT is implemented by the persistent kernel only (M=%d N=%d K=%d is below its threshold: ask dicow_gemm_nt_is_persistent)", a->M, a->N, a->K);
-    if ((variant >= 4 || (variant == 0 && big)) && a->M >= 256 && a->N >= 256) {
-        if (variant == 0 || variant >= 11) {
-            const int lim = g_gemm_cus.load();
-            const int ncu = (lim > 0 && lim < g_ncu_all) ? lim : g_ncu_all;   // CUs left to us (dicow_set_gemm_cus)
-            // tile shape: 192x320 where its whole rounds of `ncu` workgroups pad the problem less than 256x256 does AND the
-            // output is narrow (M = 24000: the N = 1280 shapes gain 2-5 %; N = 3840 is neutral and N = 5120 with the GELU
-            // epilogue loses -- more, smaller tiles mean more epilogues).  Diagnostic builds: DICOW_NT_VARIANT 21 / 22 force the
-            // ring kernel's 256x256 / 192x320 tiles, 12 / 13 the two-stage kernel's, 11 its run-time-flag epilogue
-            const int64_t t44 = (int64_t)dicow_cdiv(a->M, 256) * dicow_cdiv(a->N, 256) * batch;
-            const int64_t t35 = (int64_t)dicow_cdiv(a->M, 192) * dicow_cdiv(a->N, 320) * batch;
-            const int64_t w44 = dicow_cdiv(t44, ncu) * 256 * 256, w35 = dicow_cdiv(t35, ncu) * 192 * 320;
-            // (round 3: with the cheaper GELU the inference fc1 -- bias + GELU, no saved derivative -- gains 8 us per launch from
-            // the smaller tiles at N = 5120 too: encoder forward 38.86 -> 38.60 ms in-situ; the training epilogues still lose)
-            const bool wide_ok = a->N <= 2048 || a->flags == (DICOW_EPI_BIAS | DICOW_EPI_GELU) || a->flags == NT_FC1I_LN_FLAGS ||
-                                 ((NT_WIDE35 & 1) && (a->flags & DICOW_EPI_MUL_AUX)) ||                     // experiments: the dgrad x gelu' epilogue,
-                                 ((NT_WIDE35 & 2) && (a->flags & DICOW_EPI_GELU_DAUX)) ||                   // the training fc1,
-                                 ((NT_WIDE35 & 4) && a->flags == (DICOW_EPI_BIAS | DICOW_EPI_SCALE_N)) ||   // qkv,
-                                 ((NT_WIDE35 & 8) && a->flags == 0);                                        // plain dgrad
-            const bool fddt = (a->flags & DICOW_EPI_FDDT) != 0;      // (only the 192 x 320 instantiation carries that epilogue)
-            DICOW_REQUIRE(!fddt || ((a->flags == NT_FDDT_FLAGS || a->flags == NT_FDDT_LN_FLAGS) && variant == 0 && a->N >= 320 && batch == 1 && a->fddt_rowmask &&
-                                    a->fddt_w[0] && a->fddt_w[1] && a->fddt_w[2] && a->fddt_w[3] && a->fddt_b[0] && a->fddt_b[1] &&
-                                    a->fddt_b[2] && a->fddt_b[3]),
-                          "gemm_nt: EPI_FDDT needs BIAS | RESIDUAL | OUT_F32, N >= 320, one batch, the eight vectors and the row masks");
-            const bool lnstat = (a->flags & DICOW_EPI_LNSTAT) != 0, lnfold = (a->flags & DICOW_EPI_LNFOLD) != 0;
-            DICOW_REQUIRE(!lnstat || ((a->flags == NT_RES_LN_FLAGS || a->flags == NT_FDDT_LN_FLAGS) && variant == 0 && batch == 1 && a->aux &&
-                                      a->lnstat && a->N % 320 == 0 && a->N <= 1280 && (int64_t)a->M * 128 < (1ll << 31)),
-                          "gemm_nt: EPI_LNSTAT needs BIAS | RESIDUAL | OUT_F32 [| FDDT], aux (the bf16 copy), lnstat, N %% 320 == 0, N <= 1280 (N=%d)", a->N);
-            DICOW_REQUIRE(!lnfold || ((a->flags == NT_QKV_LN_FLAGS || a->flags == NT_FC1I_LN_FLAGS || a->flags == NT_FC1T_LN_FLAGS) && variant == 0 &&
-                                      batch == 1 && a->lnstat && a->ln_c && a->bias && a->ln_nslots > 0 && a->ln_nslots <= DICOW_LN_SLOTS &&
-                                      a->ln_nslots % 4 == 0 && a->ln_inv_dim > 0.f && (int64_t)a->M * 128 < (1ll << 31)),
-                          "gemm_nt: EPI_LNFOLD needs BIAS with SCALE_N or GELU [| GELU_DAUX], lnstat, ln_c, ln_nslots (multiple of 4, <= 16), ln_inv_dim");
-            // (round 6, interleaved A/B of the tile choice per epilogue kind -- profiles/r06_epilogues.txt: the choices above hold, except that a
-            // PLAIN product (no epilogue work at all: the dgrads of out-proj / qkv / fc1) is 1.7-2.1 % faster on 256 x 256 at N = 1280 too)
-            const bool plain256 = a->flags == 0 && !(NT_WIDE35 & 8);
-            const bool use35 = fddt || lnstat || variant == 13 || variant == 22 || (variant != 12 && variant != 21 && a->N >= 320 && wide_ok && !plain256 && w35 < w44);
-            const int total = (int)(use35 ? t35 : t44);
-            // balanced grid: with r = ceil(total / ncu) rounds needed anyway, ceil(total / r) workgroups each take r (or
-            // r - 1) tiles -- e.g. 470 tiles run on 235 workgroups x 2 instead of 214 x 2 + 42 x 1: same makespan, fewer
-            // CUs competing for L2 / HBM / power while the last round is partial (measured 0.304 -> 0.287 ms)
-            const int rounds = dicow_cdiv(total, ncu);
-            const dim3 gp(dicow_cdiv(total, rounds));
-            if (colsum_rows) *colsum_rows = 2 * dicow_cdiv(a->M, use35 ? 192 : 256);
-#ifdef DICOW_ABLATIONS
-            const bool two_stage = variant >= 11 && variant <= 13;
-#define NTW_LAUNCH(F) { if (two_stage && use35) hipLaunchKernelGGL((gemm_ntw_kernel<F, 3, 5>), gp, dim3(256), NTW_LDS, (hipStream_t)stream, *a); \
-                        else if (two_stage) hipLaunchKernelGGL((gemm_ntw_kernel<F, 4, 4>), gp, dim3(256), NTW_LDS, (hipStream_t)stream, *a); \
-                        else if (use35) hipLaunchKernelGGL((gemm_ntr_kernel<F, 3, 5>), gp, dim3(256), NTR_LDS, (hipStream_t)stream, *a); \
-                        else hipLaunchKernelGGL((gemm_ntr_kernel<F, 4, 4>), gp, dim3(256), NTR_LDS, (hipStream_t)stream, *a); }
-#else
-#define NTW_LAUNCH(F) { if (use35) hipLaunchKernelGGL((gemm_ntr_kernel<F, 3, 5>), gp, dim3(256), NTR_LDS, (hipStream_t)stream, *a); \
-                        else hipLaunchKernelGGL((gemm_ntr_kernel<F, 4, 4>), gp, dim3(256), NTR_LDS, (hipStream_t)stream, *a); }
-#endif
-#if NT_DEFER_BUILD
-            // bias + GELU [+ saved derivative] with the epilogue deferred into the next tile's k-loop (experiments/gemm_ntd.hip; round 4: bit-identical, 1.5-2 x slower -- profiles/r04_ntd_deferred_epilogue.txt): 192 x 320 tiles,
-            // at least two tiles per workgroup (the last one is flushed after the loop, nothing hides it)
-            {
-                static const int defer = dicow_ntd_mode_(NT_DEFER);            // (experiment build: the run-time switch lives in gemm_ntd.hip)
-                const bool gelu_i = a->flags == (DICOW_EPI_BIAS | DICOW_EPI_GELU), gelu_t = a->flags == (DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX);
-                const bool light = a->flags == 0 || a->flags == DICOW_EPI_BIAS || a->flags == (DICOW_EPI_BIAS | DICOW_EPI_SCALE_N);
-                const bool resid = a->flags == (DICOW_EPI_BIAS | DICOW_EPI_RESIDUAL | DICOW_EPI_OUT_F32);
-                if (variant == 0 && batch == 1 && ((gelu_i && (defer & 1)) || (gelu_t && (defer & 2)) || (light && (defer & 4)) || (resid && (defer & 8))) &&
-                    a->N % 320 == 0 && a->K >= 16 * BK && t35 > ncu) {
-                    const int rounds_d = dicow_cdiv((int)t35, ncu);
-                    // light epilogues: the un-swapped-layout kernel (gemm_ntl.hip) unless bit 16 asks for the first form; it refuses ragged M
-                    int rc = -1;
-                    if ((light || resid) && !(defer & 16)) {
-                        rc = dicow_ntl_launch_(a, dicow_cdiv((int)t35, rounds_d), stream);
-                        if (rc == 0) disp_note("gemm_ntl_kernel<%d>", a->flags);
-                    }
-                    if (rc != 0 && (gelu_i || gelu_t || (defer & 16))) {
-                        rc = dicow_ntd_launch_(a, dicow_cdiv((int)t35, rounds_d), stream);
-                        if (rc == 0) disp_note("gemm_ntd_kernel<%d>", a->flags);
-                    }
-                    if (rc == 0) {
-                        DICOW_CHECK_LAUNCH("gemm_nt (persistent, deferred epilogue)");
-                        return DICOW_OK;
-                    }
-                }
-            }
-#endif
-            if (want_colsum && variant != 11 && a->flags == DICOW_EPI_MUL_AUX) { a->flags |= DICOW_EPI_COLSUM; *fused_colsum = true; }
-#if NT_EXPERIMENT_KERNELS
-            {
-                // two workgroups per CU (gemm_nt2_kernel, 128 x 256 tiles): the epilogue-heavy shapes, per NT2_MASK
-#if defined(DICOW_ABLATIONS) || defined(DICOW_EXPERIMENTS)
-                static const int nt2_mask = getenv("DICOW_NT2_MASK") ? atoi(getenv("DICOW_NT2_MASK")) : NT2_MASK;
-                static const int nt2_delay = getenv("DICOW_NT2_DELAY") ? atoi(getenv("DICOW_NT2_DELAY")) : NT2_DELAY;
-#else
-                constexpr int nt2_mask = NT2_MASK, nt2_delay = NT2_DELAY;
-#endif
-                const int f_ = a->flags;
-                const int cls = f_ == NT_RES_FLAGS ? 1 : f_ == (DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX) ? 2 : f_ == (DICOW_EPI_BIAS | DICOW_EPI_GELU) ? 4 :
-                                (f_ == DICOW_EPI_MUL_AUX || f_ == (DICOW_EPI_MUL_AUX | DICOW_EPI_COLSUM)) ? 8 :
-                                (f_ == DICOW_EPI_BIAS || f_ == (DICOW_EPI_BIAS | DICOW_EPI_SCALE_N)) ? 16 : f_ == 0 ? 32 : 0;
-#if defined(DICOW_ABLATIONS) || defined(DICOW_EXPERIMENTS)
-                static const int ntq_mask = getenv("DICOW_NTQ_MASK") ? atoi(getenv("DICOW_NTQ_MASK")) : NTQ_MASK;
-#else
-                constexpr int ntq_mask = NTQ_MASK;
-#endif
-                {
-                    // 320 x 256 tiles (gemm_ntq_kernel): whole tiles only, at least three k-steps, and only where its rounds of `ncu`
-                    // workgroups cover no more padded area than the ring kernel's choice (M = 24000: N = 5120 -> 1500 tiles = 6 rounds)
-                    const int64_t tq = (int64_t)(a->M / 320) * (a->N / 256) * batch;
-                    const int64_t wq = dicow_cdiv(tq, ncu) * 320 * 256, wr = (a->N >= 320 && wide_ok && w35 < w44) ? w35 : w44;
-                    if (variant == 0 && (ntq_mask & cls) && a->M % 320 == 0 && a->N % 256 == 0 && a->K >= 3 * BK && tq > 0 && (wq <= wr || (ntq_mask & 1024))) {
-                        const int roundsq = dicow_cdiv(tq, ncu);
-                        const dim3 gq(dicow_cdiv(tq, roundsq));
-                        if (colsum_rows) *colsum_rows = 2 * (a->M / 320);
-                        disp_note("gemm_ntq_kernel<%d>", f_);
-#define NTQ_LAUNCH(F) hipLaunchKernelGGL((gemm_ntq_kernel<F>), gq, dim3(256), NTQ_LDS, (hipStream_t)stream, *a)
-                        switch (f_) {
-                            case 0: NTQ_LAUNCH(0); break;
-                            case DICOW_EPI_BIAS: NTQ_LAUNCH(DICOW_EPI_BIAS); break;
-                            case DICOW_EPI_BIAS | DICOW_EPI_SCALE_N: NTQ_LAUNCH(DICOW_EPI_BIAS | DICOW_EPI_SCALE_N); break;
-                            case DICOW_EPI_BIAS | DICOW_EPI_GELU: NTQ_LAUNCH(DICOW_EPI_BIAS | DICOW_EPI_GELU); break;
-                            case NT_RES_FLAGS: NTQ_LAUNCH(NT_RES_FLAGS); break;
-                            case DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX: NTQ_LAUNCH(DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX); break;
-                            case DICOW_EPI_MUL_AUX: NTQ_LAUNCH(DICOW_EPI_MUL_AUX); break;
-                            default: NTQ_LAUNCH(DICOW_EPI_MUL_AUX | DICOW_EPI_COLSUM); break;
-                        }
-#undef NTQ_LAUNCH
-                        DICOW_CHECK_LAUNCH("gemm_ntq (persistent, 320 x 256 tiles)");
-                        return DICOW_OK;
-                    }
-                }
-                if (variant == 0 && (nt2_mask & cls) && a->M >= 128 && a->N >= 256) {
-                    const int64_t t2 = (int64_t)dicow_cdiv(a->M, 128) * dicow_cdiv(a->N, 256) * batch;
-                    const int rounds2 = dicow_cdiv(t2, NT2_SLOTS * ncu);
-                    const dim3 g2(dicow_cdiv(t2, rounds2));
-                    if (colsum_rows) *colsum_rows = 2 * dicow_cdiv(a->M, 128);
-                    disp_note("gemm_nt2_kernel<%d>", f_);
-#define NT2_LAUNCH(F) hipLaunchKernelGGL((gemm_nt2_kernel<F>), g2, dim3(256), NT2_LDS, (hipStream_t)stream, *a, nt2_delay)
-                    switch (f_) {
-                        case 0: NT2_LAUNCH(0); break;
-                        case DICOW_EPI_BIAS: NT2_LAUNCH(DICOW_EPI_BIAS); break;
-                        case DICOW_EPI_BIAS | DICOW_EPI_SCALE_N: NT2_LAUNCH(DICOW_EPI_BIAS | DICOW_EPI_SCALE_N); break;
-                        case DICOW_EPI_BIAS | DICOW_EPI_GELU: NT2_LAUNCH(DICOW_EPI_BIAS | DICOW_EPI_GELU); break;
-                        case NT_RES_FLAGS: NT2_LAUNCH(NT_RES_FLAGS); break;
-                        case DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX: NT2_LAUNCH(DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX); break;
-                        case DICOW_EPI_MUL_AUX: NT2_LAUNCH(DICOW_EPI_MUL_AUX); break;
-                        default: NT2_LAUNCH(DICOW_EPI_MUL_AUX | DICOW_EPI_COLSUM); break;
-                    }
-#undef NT2_LAUNCH
-                    DICOW_CHECK_LAUNCH("gemm_nt2 (persistent, two workgroups per CU)");
-                    return DICOW_OK;
-                }
-            }
-#endif
-            {
-                const int f_ = a->flags;
-                const bool ct_ = variant != 11 && (f_ == 0 || f_ == DICOW_EPI_BIAS || f_ == (DICOW_EPI_BIAS | DICOW_EPI_SCALE_N) || f_ == (DICOW_EPI_BIAS | DICOW_EPI_GELU) ||
-                                                   f_ == (DICOW_EPI_BIAS | DICOW_EPI_RESIDUAL | DICOW_EPI_OUT_F32) || f_ == (DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX) ||
-                                                   f_ == DICOW_EPI_MUL_AUX || f_ == (DICOW_EPI_MUL_AUX | DICOW_EPI_COLSUM) || f_ == NT_FDDT_FLAGS ||
-                                                   f_ == NT_RES_LN_FLAGS || f_ == NT_FDDT_LN_FLAGS || f_ == NT_QKV_LN_FLAGS || f_ == NT_FC1I_LN_FLAGS || f_ == NT_FC1T_LN_FLAGS);
-                disp_note("gemm_ntr_kernel<%d, %d, %d>", ct_ ? f_ : -1, use35 ? 3 : 4, use35 ? 5 : 4);
-            }
-            switch (variant == 11 ? -1 : a->flags) {   // compile-time epilogues for the flag sets the training step uses
-                case 0: NTW_LAUNCH(0); break;
-                case DICOW_EPI_BIAS: NTW_LAUNCH(DICOW_EPI_BIAS); break;
-                case DICOW_EPI_BIAS | DICOW_EPI_SCALE_N: NTW_LAUNCH(DICOW_EPI_BIAS | DICOW_EPI_SCALE_N); break;
-                case DICOW_EPI_BIAS | DICOW_EPI_GELU: NTW_LAUNCH(DICOW_EPI_BIAS | DICOW_EPI_GELU); break;
-                case DICOW_EPI_BIAS | DICOW_EPI_RESIDUAL | DICOW_EPI_OUT_F32: NTW_LAUNCH(DICOW_EPI_BIAS | DICOW_EPI_RESIDUAL | DICOW_EPI_OUT_F32); break;
-                case DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX: NTW_LAUNCH(DICOW_EPI_BIAS | DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX); break;
-                case NT_FDDT_FLAGS: hipLaunchKernelGGL((gemm_ntr_kernel<NT_FDDT_FLAGS, 3, 5>), gp, dim3(256), NTR_LDS, (hipStream_t)stream, *a); break;
-#ifdef DICOW_EXPERIMENTS
-                case NT_RES_LN_FLAGS: hipLaunchKernelGGL((gemm_ntr_kernel<NT_RES_LN_FLAGS, 3, 5>), gp, dim3(256), NTR_LDS, (hipStream_t)stream, *a); break;
-                case NT_FDDT_LN_FLAGS: hipLaunchKernelGGL((gemm_ntr_kernel<NT_FDDT_LN_FLAGS, 3, 5>), gp, dim3(256), NTR_LDS, (hipStream_t)stream, *a); break;
-                case NT_QKV_LN_FLAGS: NTW_LAUNCH(NT_QKV_LN_FLAGS); break;
-                case NT_FC1I_LN_FLAGS: NTW_LAUNCH(NT_FC1I_LN_FLAGS); break;
-                case NT_FC1T_LN_FLAGS: NTW_LAUNCH(NT_FC1T_LN_FLAGS); break;
-#endif
-                case DICOW_EPI_MUL_AUX: NTW_LAUNCH(DICOW_EPI_MUL_AUX); break;
-                case DICOW_EPI_MUL_AUX | DICOW_EPI_COLSUM: NTW_LAUNCH(DICOW_EPI_MUL_AUX | DICOW_EPI_COLSUM); break;
-                default: NTW_LAUNCH(-1); break;
-            }
-#undef NTW_LAUNCH
+    rc = nt_check_ring_epilogues(a, p, knobs.variant);
+    if (rc != DICOW_OK) return rc;
+    rc = nt_experiment_route(a, p, knobs.variant, want_colsum, fused_colsum, colsum_rows, stream);
+    if (rc != NT_NOT_ROUTED) return rc;
+    switch (p.family) {
+        case NT_FAM_RING: {
+            nt_fuse_colsum(a, want_colsum, fused_colsum);
+            if (colsum_rows) *colsum_rows = p.colsum_rows;
+            const int ct = nt_ct_flags(a->flags);
+            disp_note("gemm_ntr_kernel<%d, %d, %d>", ct, p.use35 ? 3 : 4, p.use35 ? 5 : 4);
+            ntr_launch(ct, p.use35, dim3(p.grid), stream, *a);
+            DICOW_CHECK_LAUNCH("gemm_nt (persistent)");
+            return DICOW_OK;
         }
-#ifdef DICOW_ABLATIONS
-        else {
-            const dim3 g256(dicow_cdiv(a->M, 256) * dicow_cdiv(a->N, 256), 1, batch);
-            if (variant == 9) hipLaunchKernelGGL(gemm_nt256s_kernel, g256, dim3(512), NTS_LDS, (hipStream_t)stream, *a);
-            else if (variant == 5) hipLaunchKernelGGL(gemm_nt256_kernel<1>, g256, dim3(512), NT256_LDS, (hipStream_t)stream, *a);
-            else if (variant == 6) hipLaunchKernelGGL(gemm_nt256_kernel<2>, g256, dim3(512), NT256_LDS, (hipStream_t)stream, *a);
-            else if (variant == 7) hipLaunchKernelGGL(gemm_nt256_kernel<3>, g256, dim3(512), NT256_LDS, (hipStream_t)stream, *a);
-            else if (variant == 8) hipLaunchKernelGGL(gemm_nt256_kernel<4>, g256, dim3(512), NT256_LDS, (hipStream_t)stream, *a);
-            else hipLaunchKernelGGL(gemm_nt256_kernel<0>, g256, dim3(512), NT256_LDS, (hipStream_t)stream, *a);
-        }
-#endif
-        DICOW_CHECK_LAUNCH("gemm_nt (persistent)");
-        return DICOW_OK;
-    }
-    const dim3 grid(ntm * ntn, 1, batch);
-    // (32-bit byte offsets inside one batch slice of A / B, as the persistent kernel needs them)
-    const bool t128 = NT128_THREADED && (int64_t)a->M * a->lda * 2 < (1ll << 31) && (int64_t)a->N * a->ldb * 2 < (1ll << 31) && a->K >= 2 * BK;
-    // few 128 x 128 tiles (the decoder at training time: M = batch x label length): 64 x 64 tiles on a deep ring (gemm_nt64_kernel)
-    const int64_t t64 = (int64_t)dicow_cdiv(a->M, 64) * dicow_cdiv(a->N, 64) * batch;
-    const int64_t tw = (int64_t)dicow_cdiv(a->M, 128) * dicow_cdiv(a->N, 256) * batch;      // 128 x 256 tiles (gemm_nt128w_kernel)
-#ifdef DICOW_ABLATIONS
-    if (variant == 1) hipLaunchKernelGGL((gemm_nt_kernel<1, false>), grid, dim3(256), 2 * STAGE_BYTES, (hipStream_t)stream, *a);
-    else if (variant == 2) hipLaunchKernelGGL((gemm_nt_kernel<2, true>), grid, dim3(256), NT_LDS_BYTES, (hipStream_t)stream, *a);
-    else if (variant == 3) hipLaunchKernelGGL((gemm_nt_kernel<1, true>), grid, dim3(256), 2 * STAGE_BYTES, (hipStream_t)stream, *a);
-    else
-#endif
-    if (NT64_MAX_TILES128 > 0 && t128 && variant == 0 &&
-        ((int64_t)ntm * ntn * batch <= NT64_MAX_TILES128 || (a->K <= NT64_SMALLK && (int64_t)ntm * ntn * batch <= NT64_SMALLK_TILES128))) {
-        const dim3 g64(dicow_cdiv(a->M, 64) * dicow_cdiv(a->N, 64), 1, batch);
-        if (NT64_DEEP_ALWAYS || t64 <= g_ncu_all) {   // one workgroup per CU anyway: the whole 128 KiB ring
-            hipLaunchKernelGGL(gemm_nt64_kernel<8>, g64, dim3(256), 8 * 16384, (hipStream_t)stream, *a);
-            disp_note("gemm_nt64_kernel<8>");
-        } else {
-            hipLaunchKernelGGL(gemm_nt64_kernel<4>, g64, dim3(256), 4 * 16384, (hipStream_t)stream, *a);
-            disp_note("gemm_nt64_kernel<4>");
-        }
-#if NT128W
-    } else if (t128 && variant == 0 && a->N >= 256 && a->M >= 128 && tw >= NT128W_MIN_TILES &&
-               tw * 10 >= dicow_cdiv(tw, g_ncu_all) * g_ncu_all * 7) {    // its (one workgroup per CU) rounds at least 70 % full
-        const dim3 gw(dicow_cdiv(a->M, 128) * dicow_cdiv(a->N, 256), 1, batch);
-        hipLaunchKernelGGL(gemm_nt128w_kernel, gw, dim3(256), NT128W_LDS, (hipStream_t)stream, *a);
-        disp_note("gemm_nt128w_kernel");
-#endif
-    } else if (t128) {
-        hipLaunchKernelGGL(gemm_nt128t_kernel, grid, dim3(256), NT_LDS_BYTES, (hipStream_t)stream, *a);
-        disp_note("gemm_nt128t_kernel");
-    } else {
-        hipLaunchKernelGGL((gemm_nt_kernel<2, false>), grid, dim3(256), NT_LDS_BYTES, (hipStream_t)stream, *a);
-        disp_note("gemm_nt_kernel<2, false>");
+        case NT_FAM_64:
+            if (p.stages64 == 8) hipLaunchKernelGGL(gemm_nt64_kernel<8>, grid, dim3(256), 8 * 16384, stream, *a);
+            else hipLaunchKernelGGL(gemm_nt64_kernel<4>, grid, dim3(256), 4 * 16384, stream, *a);
+            disp_note("gemm_nt64_kernel<%d>", p.stages64);
+            break;
+        case NT_FAM_128T:
+            hipLaunchKernelGGL(gemm_nt128t_kernel, grid, dim3(256), NT_LDS_BYTES, stream, *a);
+            disp_note("gemm_nt128t_kernel");
+            break;
+        default:
+            hipLaunchKernelGGL((gemm_nt_kernel<2, false>), grid, dim3(256), NT_LDS_BYTES, stream, *a);
+            disp_note("gemm_nt_kernel<2, false>");
+            break;
     }
     DICOW_CHECK_LAUNCH("gemm_nt");
     return DICOW_OK;
