@@ -115,6 +115,9 @@ typedef struct {
     float eps;
 } dicow_fddt_ln_fwd_args;
 int dicow_fddt_ln_fwd(const dicow_fddt_ln_fwd_args* a, void* stream);
+/* Which kernel body dicow_fddt_ln_fwd runs these arguments on -- "staged", "init_wave", "ln_wave", "generic_ln", "generic_diag",
+   "generic" or "generic_1024" -- or NULL where it would reject them (dicow_last_error says why).  Host arithmetic only: launches nothing. */
+const char* dicow_fddt_ln_fwd_route(const dicow_fddt_ln_fwd_args* a);
 
 /* Backward of the same fused row op (+ residual-gradient add):
  *   g   = g_res + LayerNormBackward(d_y; x, mean, rstd, ln_w)          (x = FDDT(h_in)+pos, recomputed)
@@ -144,6 +147,9 @@ typedef struct {
 } dicow_fddt_ln_bwd_args;
 int64_t dicow_fddt_ln_bwd_ws_bytes(int rows, int D);
 int dicow_fddt_ln_bwd(const dicow_fddt_ln_bwd_args* a, void* stream);
+/* ... dicow_fddt_ln_bwd: "ln_wave", "staged_bf16", "staged_f32", "ln_only", "generic" or "generic_1024"; NULL where the arguments are
+   rejected (the workspace size is checked by the launch, not here) */
+const char* dicow_fddt_ln_bwd_route(const dicow_fddt_ln_bwd_args* a);
 
 /* Full (D x D) FDDT combine: y4 = h @ [W_S;W_T;W_N;W_O]^T (bf16 [rows,4D], from dicow_gemm_nt with bias) ->
  * h' = sum_c m_c * y4[:, cD:(c+1)D]; disabled classes pass y4 block = h via use_mask.  (FDDT.py:13-16, 53-62) */

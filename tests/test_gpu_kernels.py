@@ -607,3 +607,119 @@ def test_attn_fwd_single_query_row(ops, B, H, Lk):
     s = torch.einsum("bqhd,bkhd->bhqk", q.float(), k)
     ref = torch.einsum("bhqk,bkhd->bqhd", torch.softmax(s, -1), v)
     assert maxdiff(o.float().cpu(), ref) < 2e-2
+
+
+# ------------------------------------------------------------------------------------------------ row-kernel routes at small shapes
+# (D, B, T) -> the bodies the four calls of an encoder layer must run on: FDDT+LN forward, FDDT+LN backward (with / without the bf16
+# copy: staged_bf16 / staged_f32), LN-only forward, LN-only backward
+ROW_ROUTE_CASES = {
+    (256, 1, 5): ("staged", "staged", "generic_ln", "ln_only"),              # one wave, fewer rows than one trip
+    (1280, 2, 1031): ("staged", "staged", "ln_wave", "ln_wave"),             # 2062 rows: not a multiple of 3 or 4, more than the forward's 512 x 4
+                                                                             # and the backward's 256 x 4 -- workgroups loop, the prefetch runs
+    (2048, 1, 7): ("staged", "staged", "generic_ln", "ln_only"),             # the widest staged width
+    (1536, 1, 9): ("staged", "staged", "generic_ln", "ln_only"),             # staged FDDT+LN, LN-only on the generic body
+    (2304, 1, 6): ("generic_1024",) * 4,                                     # the 1024-thread body
+}
+# Bounds: the expressions of test_layer_row_kernels_at_bench_size (set at D = 1280); the column sums' scale with sqrt(rows).  Measured on
+# the library as it was before the dispatch became a plan, worst over the five shapes: h_out 6.2e-7, bf16 1.56e-2, g_out 1.3e-6, sums
+# 3.5e-5 at 2062 rows and 1.8e-6 at 5..9 rows -- every width below half its bound, so none is widened (profiles/r08_rows_dispatch_refactor_ab.txt).
+ROW_BOUNDS = dict(h_out=2e-6, bf16=5e-2, g_out=5e-4, ln_sums=5e-4, fddt_sums=8e-4)
+
+
+class _ExpectRoute:
+    """While active, every dicow_fddt_ln_fwd / _bwd call first asks the library which body it will run and fails unless it is `want`."""
+    def __init__(self, want):
+        self.want = want
+
+    def __enter__(self):
+        import ctypes as C
+        from ts_asr_whisper_amd import _lib as L
+        self.L, self.orig = L, L.call_struct
+
+        def call_struct(name, st):
+            got = getattr(L.lib(), name + "_route")(C.byref(st))
+            assert got is not None and got.decode() == self.want, (name, got, self.want)
+            self.orig(name, st)
+        L.call_struct = call_struct
+
+    def __exit__(self, *exc):
+        self.L.call_struct = self.orig
+
+
+def row_route_case_errors(ops, D, B, T, routes=None):
+    """One encoder layer's four row-kernel calls at a small shape against torch on the CPU in fp64; returns the worst absolute error
+    of every output.  `routes`: the expected bodies (None: do not ask -- a library without the route queries)."""
+    import contextlib
+    rows = B * T
+    expect = (lambda r: _ExpectRoute(r)) if routes else (lambda r: contextlib.nullcontext())
+    fwd_r, bwd_r, lnf_r, lnb_r = routes or (None,) * 4
+    g = torch.Generator().manual_seed(D + rows)
+    rnd = lambda *s: torch.randn(*s, generator=g)
+    h, st = rnd(rows, D), torch.softmax(rnd(B, 4, T), 1)
+    w, b = [1 + 0.1 * rnd(D) for _ in range(4)], [0.1 * rnd(D) for _ in range(4)]
+    lw, lb = 1 + 0.1 * rnd(D), 0.1 * rnd(D)
+    dy, gres = rnd(rows, D).bfloat16(), rnd(rows, D)
+    f64 = lambda t: t.double().clone().requires_grad_(True)
+    hr, wr, br, lwr, lbr = f64(h), [f64(t) for t in w], [f64(t) for t in b], f64(lw), f64(lb)
+    x = sum((hr.view(B, T, D) * wr[c] + br[c]) * st.double()[:, c, :, None] for c in range(4)).view(rows, D)
+    y = torch.nn.functional.layer_norm(x, (D,), lwr, lbr)
+    ((y * dy.double()).sum() + (x * gres.double()).sum()).backward()
+    xl, lw2 = f64(x.detach().float()), f64(lw)
+    yl = torch.nn.functional.layer_norm(xl, (D,), lw2, lb.double())
+    ((yl * dy.double()).sum() + (xl * gres.double()).sum()).backward()
+    err = {}
+    worst = lambda got, ref: float((got.double().cpu() - ref.detach()).abs().max())
+    cu = lambda t: t.cuda()
+    hg, stg, wg, bg, lwg, lbg, dyg, gresg = cu(h), cu(st), [cu(t) for t in w], [cu(t) for t in b], cu(lw), cu(lb), cu(dy), cu(gres)
+    new = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device="cuda")
+    # ---- forward: FDDT + LN, and LN only
+    ho, yb, mean, rstd = new(rows, D), new(rows, D, dtype=torch.bfloat16), new(rows), new(rows)
+    with expect(fwd_r):
+        ops.fddt_ln_fwd(hg, rows, D, mode=ops.MODE_DIAG, stno=stg, T=T, w=wg, b=bg, h_out=ho, ln_w=lwg, ln_b=lbg, y_bf16=yb, mean=mean, rstd=rstd)
+    err["fwd.h_out"], err["fwd.y_bf16"] = worst(ho, x), worst(yb, y)
+    xg = cu(x.detach().float())
+    y2, m2, r2 = new(rows, D, dtype=torch.bfloat16), new(rows), new(rows)
+    with expect(lnf_r):
+        ops.fddt_ln_fwd(xg, rows, D, mode=ops.MODE_NONE, ln_w=lwg, ln_b=lbg, y_bf16=y2, mean=m2, rstd=r2)
+    err["ln_fwd.y_bf16"], err["ln_fwd.mean"] = worst(y2, yl), worst(m2, xl.mean(-1))
+    # ---- backward: LN + residual + FDDT, with and without the bf16 copy
+    for want_bf16 in (True, False):
+        tag = "bwd_bf16." if want_bf16 else "bwd_f32."
+        g0, g0b = new(rows, D), (new(rows, D, dtype=torch.bfloat16) if want_bf16 else None)
+        dlw, dlb, cs, dw, db = new(D), new(D), new(D), [new(D) for _ in range(4)], [new(D) for _ in range(4)]
+        with expect(bwd_r + ("_bf16" if want_bf16 else "_f32") if bwd_r == "staged" else bwd_r):
+            ops.fddt_ln_bwd(hg, rows, D, mode=ops.MODE_DIAG, stno=stg, T=T, w=wg, b=bg, ln_w=lwg, mean=mean, rstd=rstd, d_y=dyg, g_res=gresg,
+                            g_out=g0, g_out_bf16=g0b, dln_w=dlw, dln_b=dlb, dw=dw, db=db, colsum_out=cs)
+        err[tag + "g_out"] = worst(g0, hr.grad)
+        if want_bf16:
+            err[tag + "g_out_bf16"] = worst(g0b, hr.grad)
+        err[tag + "ln_sums"] = max(worst(dlw, lwr.grad), worst(dlb, lbr.grad))
+        err[tag + "fddt_sums"] = max([worst(dw[c], wr[c].grad) for c in range(4)] + [worst(db[c], br[c].grad) for c in range(4)] +
+                                     [worst(cs, hr.grad.sum(0))])
+    # ---- backward: LN only (the second LayerNorm of a layer) with the residual gradient
+    g1, g1b, dlw, dlb, cs = new(rows, D), new(rows, D, dtype=torch.bfloat16), new(D), new(D), new(D)
+    with expect(lnb_r):
+        ops.fddt_ln_bwd(xg, rows, D, mode=ops.MODE_NONE, ln_w=lwg, mean=m2, rstd=r2, d_y=dyg, g_res=gresg, g_out=g1, g_out_bf16=g1b,
+                        dln_w=dlw, dln_b=dlb, colsum_out=cs)
+    err["ln_bwd.g_out"], err["ln_bwd.g_out_bf16"] = worst(g1, xl.grad), worst(g1b, xl.grad)
+    err["ln_bwd.ln_sums"] = max(worst(dlw, lw2.grad), worst(dlb, dy.double().sum(0)))
+    err["ln_bwd.fddt_sums"] = worst(cs, xl.grad.sum(0))
+    return err
+
+
+@pytest.mark.parametrize("D,B,T", list(ROW_ROUTE_CASES))
+def test_row_kernel_routes_at_small_shapes(ops, D, B, T):
+    """Every row-kernel body an encoder layer can be routed to, at the smallest shapes that reach it (the bench-sized test only covers
+    D = 1280): forward FDDT+LN without pos / y_f32, backward with and without the bf16 copy, LN-only forward and backward, against
+    torch on the CPU in fp64.  Each call first asserts the body it is about to run, so a routing change fails here instead of
+    quietly testing another kernel."""
+    err = row_route_case_errors(ops, D, B, T, ROW_ROUTE_CASES[(D, B, T)])
+    sc = (B * T) ** 0.5
+    bounds = {}
+    for name in err:
+        kind = name.split(".")[1]
+        bounds[name] = (ROW_BOUNDS["bf16"] if kind.endswith("bf16") else 1e-5 if kind == "mean" else
+                        ROW_BOUNDS[kind] * sc if kind.endswith("sums") else ROW_BOUNDS[kind])
+        print(f"rows D={D} rows={B * T} {name}: {err[name]:.3e} (bound {bounds[name]:.3e})")
+    for name, e in err.items():
+        assert e < bounds[name], (name, e, bounds[name])

@@ -69,6 +69,137 @@ def test_gemm_nt_is_persistent_host_logic():
     assert _lib.EPI_FDDT == 1024 and C.sizeof(_lib.GemmArgs) % 8 == 0
 
 
+# ------------------------------------------------------------------------------------------------ row-kernel routing
+_PTR = 1 << 20          # null-but-nonzero dummy pointer: the plans read pointers only as present / absent
+_ROW_WIDTHS = (252, 256, 1280, 1536, 2048, 2052, 2304, 4096)
+
+
+def _rows_fwd_args(D, rows=8, mode=1, ln=True, in_bf16=False, h_out=True, y_bf16=True, y_f32=False, stats=True, pos=False, missing=None):
+    from ts_asr_whisper_amd import _lib
+    a = _lib.FddtLnFwdArgs()
+    a.h_in, a.in_bf16, a.mode, a.rows, a.D, a.T, a.eps = _PTR, int(in_bf16), mode, rows, D, 4, 1e-5
+    if mode != 0:
+        a.stno, a.stno_bstride = _PTR, 16
+        for c in range(4):
+            a.w[c] = _PTR if mode == 1 and missing != ("w", c) else None
+            a.b[c] = _PTR if missing != ("b", c) else None
+    a.pos, a.h_out = (_PTR if pos else None), (_PTR if h_out else None)
+    a.ln_w = a.ln_b = _PTR if ln else None
+    a.y_bf16, a.y_f32 = (_PTR if y_bf16 else None), (_PTR if y_f32 else None)
+    a.mean = a.rstd = _PTR if stats else None
+    return a
+
+
+def _rows_bwd_args(D, rows=8, mode=1, ln=True, in_bf16=False, dy_f32=False, g_res=True, g_out=True, g_out_bf16=True, pos=False, missing=None):
+    from ts_asr_whisper_amd import _lib
+    a = _lib.FddtLnBwdArgs()
+    a.h_in, a.in_bf16, a.mode, a.rows, a.D, a.T = _PTR, int(in_bf16), mode, rows, D, 4
+    if mode != 0:
+        a.stno, a.stno_bstride = _PTR, 16
+        for c in range(4):
+            a.w[c] = _PTR if mode == 1 and missing != ("w", c) else None
+            a.b[c] = _PTR if missing != ("b", c) else None
+    a.pos = _PTR if pos else None
+    if ln:
+        a.ln_w = a.mean = a.rstd = a.d_y = _PTR
+    a.dy_f32 = int(dy_f32)
+    a.g_res, a.g_out, a.g_out_bf16 = (_PTR if g_res else None), (_PTR if g_out else None), (_PTR if g_out_bf16 else None)
+    return a
+
+
+# Expected routes, read off the dispatchers' conditions as they stood before the plans existed (block = D / 4 threads rounded up to
+# a wave; "wave width" = D a multiple of 256 in 512..1280):
+#   forward   staged       block <= 512, block * 4 == D, mode 1, LayerNorm, fp32 in, h_out, y_bf16, no y_f32, mean + rstd, no pos, all
+#                          eight FDDT vectors, rows * D * 4 < 2^31
+#             init_wave    mode 1, no LayerNorm, bf16 in, h_out, pos, no y, wave width, all eight vectors
+#             ln_wave      mode 0, LayerNorm, fp32 in, no h_out, no pos, wave width, some y
+#             generic_*    block > 512: generic_1024; else by mode: 0 generic_ln, 1 generic_diag, 2 generic
+#   backward  ln_wave      block <= 512, mode 0, LayerNorm, fp32 in, no pos, wave width, g_out or g_out_bf16
+#             generic_1024 block > 512
+#             staged_*     block <= 512, block * 4 == D, mode 1, LayerNorm, fp32 in, bf16 d_y, g_res, g_out, no pos, all eight vectors,
+#                          rows * D * 4 < 2^31; _bf16 with g_out_bf16, _f32 without
+#             ln_only      block <= 512, mode 0, LayerNorm;   generic: the rest
+# rows * D is a multiple of 256 wherever the byte guard decides, so the last size below 2^31 is 2^31 - 1024 (D = 256), not 2^31 - 4.
+_LAYER, _INIT, _LN = {}, dict(ln=False, in_bf16=True, y_bf16=False, stats=False, pos=True), dict(mode=0, h_out=False)
+_ROWS_FWD_ROUTES = [
+    (252, _LAYER, "generic_diag"), (256, _LAYER, "staged"), (1280, _LAYER, "staged"), (1536, _LAYER, "staged"), (2048, _LAYER, "staged"),
+    (2052, _LAYER, "generic_1024"), (2304, _LAYER, "generic_1024"), (4096, _LAYER, "generic_1024"),
+    (1280, dict(pos=True), "generic_diag"), (1280, dict(y_f32=True), "generic_diag"), (1280, dict(in_bf16=True), "generic_diag"),
+    (1280, dict(missing=("w", 2)), "generic_diag"), (1280, dict(missing=("b", 3)), "generic_diag"), (1280, dict(stats=False), "generic_diag"),
+    (1280, dict(y_bf16=False, y_f32=True), "generic_diag"), (1280, dict(h_out=False), "generic_diag"),
+    (256, dict(rows=(1 << 21) - 1), "staged"), (256, dict(rows=1 << 21), "generic_diag"),
+    (252, _INIT, "generic_diag"), (256, _INIT, "generic_diag"), (512, _INIT, "init_wave"), (1280, _INIT, "init_wave"), (1536, _INIT, "generic_diag"),
+    (2048, _INIT, "generic_diag"), (2052, _INIT, "generic_1024"), (2304, _INIT, "generic_1024"), (4096, _INIT, "generic_1024"),
+    (1280, dict(_INIT, pos=False), "generic_diag"), (1280, dict(_INIT, in_bf16=False), "generic_diag"),
+    (1280, dict(_INIT, missing=("b", 0)), "generic_diag"), (1280, dict(_INIT, y_f32=True), "generic_diag"),
+    (252, _LN, "generic_ln"), (256, _LN, "generic_ln"), (512, _LN, "ln_wave"), (1280, _LN, "ln_wave"), (1536, _LN, "generic_ln"),
+    (2048, _LN, "generic_ln"), (2052, _LN, "generic_1024"), (2304, _LN, "generic_1024"), (4096, _LN, "generic_1024"),
+    (1280, dict(_LN, y_bf16=False, y_f32=True), "ln_wave"), (1280, dict(_LN, y_f32=True), "ln_wave"), (1280, dict(_LN, h_out=True), "generic_ln"),
+    (1280, dict(_LN, in_bf16=True), "generic_ln"), (1280, dict(_LN, pos=True), "generic_ln"),
+    (1280, dict(mode=2), "generic"), (252, dict(mode=2), "generic"), (2304, dict(mode=2), "generic_1024"),
+    (1280, dict(mode=0, ln=False, y_bf16=False, stats=False), "generic_ln"),              # a plain copy
+    (1282, _LAYER, None), (4100, _LAYER, None), (1280, dict(rows=0), None), (1280, dict(mode=3), None),
+    (1280, dict(ln=False, h_out=False, y_bf16=False), None),
+]
+_BLN = dict(mode=0)
+_ROWS_BWD_ROUTES = [
+    (252, _LAYER, "generic"), (256, _LAYER, "staged_bf16"), (1280, _LAYER, "staged_bf16"), (1536, _LAYER, "staged_bf16"),
+    (2048, _LAYER, "staged_bf16"), (2052, _LAYER, "generic_1024"), (2304, _LAYER, "generic_1024"), (4096, _LAYER, "generic_1024"),
+    (256, dict(g_out_bf16=False), "staged_f32"), (1280, dict(g_out_bf16=False), "staged_f32"), (2048, dict(g_out_bf16=False), "staged_f32"),
+    (252, dict(g_out_bf16=False), "generic"), (2304, dict(g_out_bf16=False), "generic_1024"),
+    (1280, dict(missing=("w", 0)), "generic"), (1280, dict(missing=("b", 1)), "generic"), (1280, dict(dy_f32=True), "generic"),
+    (1280, dict(in_bf16=True), "generic"), (1280, dict(pos=True), "generic"), (1280, dict(g_res=False), "generic"),
+    (1280, dict(g_out=False), "generic"), (1280, dict(ln=False), "generic"),
+    (256, dict(rows=(1 << 21) - 1), "staged_bf16"), (256, dict(rows=1 << 21), "generic"),
+    (252, _BLN, "ln_only"), (256, _BLN, "ln_only"), (512, _BLN, "ln_wave"), (1280, _BLN, "ln_wave"), (1536, _BLN, "ln_only"),
+    (2048, _BLN, "ln_only"), (2052, _BLN, "generic_1024"), (2304, _BLN, "generic_1024"), (4096, _BLN, "generic_1024"),
+    (1280, dict(_BLN, g_out_bf16=False), "ln_wave"), (1280, dict(_BLN, g_out=False), "ln_wave"),
+    (1280, dict(_BLN, g_out=False, g_out_bf16=False), "ln_only"), (1280, dict(_BLN, in_bf16=True), "ln_only"),
+    (1280, dict(_BLN, pos=True), "ln_only"), (1280, dict(_BLN, g_res=False), "ln_wave"),
+    (1280, dict(mode=0, ln=False), "generic"), (1280, dict(mode=2), "generic"), (2304, dict(mode=2), "generic_1024"),
+    (1282, _LAYER, None), (4100, _LAYER, None), (1280, dict(rows=0), None), (1280, dict(mode=3), None),
+    (1280, dict(mode=0, ln=False, g_res=False), None),
+]
+
+
+def test_row_kernel_routes_host_logic():
+    """dicow_fddt_ln_fwd_route / _bwd_route are host logic (no launch): every kernel body is reached by the arguments that reached it
+    before the dispatch was a plan, on both sides of every boundary -- width, pos / y_f32 / in_bf16, a missing FDDT vector, the bf16
+    gradient copy, the 2 GiB guard of the LDS-staged bodies -- and rejected arguments answer NULL."""
+    import ctypes as C
+    from ts_asr_whisper_amd import _lib
+    lib = _lib.lib()
+    for table, build, query in ((_ROWS_FWD_ROUTES, _rows_fwd_args, lib.dicow_fddt_ln_fwd_route),
+                                (_ROWS_BWD_ROUTES, _rows_bwd_args, lib.dicow_fddt_ln_bwd_route)):
+        seen = set()
+        for D, kw, want in table:
+            got = query(C.byref(build(D, **kw)))
+            assert (got.decode() if got is not None else None) == want, (build.__name__, D, kw, got, want)
+            seen.add(want)
+            seen.add(D)
+        assert seen >= set(_ROW_WIDTHS)
+        bodies = ({"staged", "init_wave", "ln_wave", "generic_ln", "generic_diag", "generic", "generic_1024"} if build is _rows_fwd_args
+                  else {"ln_wave", "staged_bf16", "staged_f32", "ln_only", "generic", "generic_1024"})
+        assert seen >= bodies | {None}
+    assert query(None) is None
+
+
+def test_row_backward_workspace_covers_every_route():
+    """dicow_fddt_ln_bwd_ws_bytes holds the [workgroup][11][D] partial column sums of whichever backward body runs: a workgroup per 4
+    rows, at most 256 x (4 LayerNorm-only / 1 staged / 2 generic; always 4 up to 256 threads) of them; the wave-per-row body one per
+    8 rows, never more than the LayerNorm-only body."""
+    from ts_asr_whisper_amd import _lib
+    lib = _lib.lib()
+    for rows in (1, 5, 1024, 1025, 24000):
+        for D in _ROW_WIDTHS:
+            block = (D // 4 + 63) // 64 * 64
+            grids = [min((rows + 3) // 4, 256 * (4 if block <= 256 else per_cu)) for per_cu in (4, 1, 2)]
+            grids.append(min((rows + 7) // 8, grids[0]))
+            got = lib.dicow_fddt_ln_bwd_ws_bytes(rows, D)
+            assert got >= max(grids) * 11 * D * 4, (rows, D, got)
+            assert got == grids[0] * 11 * D * 4, (rows, D, got)          # and no more than the largest of them
+
+
 def test_no_cpu_fallback_and_oracle_not_imported_by_product():
     src_dir = os.path.join(ROOT, "ts-asr-whisper_amd")
     for fn in os.listdir(src_dir):

@@ -190,6 +190,10 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = at
             fn.restype = c_i64
+        for name, at in _SIGS_STR.items():
+            fn = getattr(l, name)
+            fn.argtypes = at
+            fn.restype = C.c_char_p
         l._dicow_experimental = True
         for name, at in _SIGS_EXPERIMENTAL.items():
             try:
@@ -224,8 +228,14 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
 }
 
 
+_SIGS_STR = {   # functions returning const char* (a static name, or NULL)
+    "dicow_fddt_ln_fwd_route": [C.POINTER(FddtLnFwdArgs)],
+    "dicow_fddt_ln_bwd_route": [C.POINTER(FddtLnBwdArgs)],
+}
+
+
 def declared_symbols():
-    return ["dicow_abi_version", "dicow_last_error"] + list(_SIGS) + list(_SIGS64)
+    return ["dicow_abi_version", "dicow_last_error"] + list(_SIGS) + list(_SIGS64) + list(_SIGS_STR)
 
 
 def check(rc, what):

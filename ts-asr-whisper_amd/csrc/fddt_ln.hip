@@ -9,44 +9,26 @@
 // Rows are visited R at a time (R independent 16-byte loads in flight per thread); row statistics use one
 // wave-shuffle + LDS reduction per R rows.  Algorithmic HBM bytes per row: fwd  D*(4 in + 4 out + 2 ln-out),
 // bwd  D*(4 h_in + 2 d_y + 4 g_res + 4 g_out + 2 g_out_bf16).
-#include <stdlib.h>
+//
+// The tuning values below are settled: each carries the measurement that closed it, and the diagnostic builds that varied them
+// are gone (their results: profiles/r02_ablations.txt, r03_cache_policy.txt, r03_rows_wave.txt, r03_rows_depth.txt, r06_rows.txt).
 #include "common.h"
 
 #define MAX_WAVES 16
-#ifndef ROWS_GATHER
-#define ROWS_GATHER 2      // staged forward: partials read back two waves at a time (78 -> 62 us; all at once: 88 us, register cliff)
-#endif
-#ifndef ROWS_G_FWD
-#define ROWS_G_FWD 2       // LayerNorm-only forward: two at a time (40 -> 30.5 us; all at once 33 us)
-#endif
-#ifndef ROWS_G_BWD
-#define ROWS_G_BWD 0       // LayerNorm-only / generic backward: the plain loop
-#endif
-#ifndef ROWS_G_BWDS
-#define ROWS_G_BWDS 16     // staged backward: all at once
-#endif
-
-
-struct f4 { float x, y, z, w; };
+// per-wave partials of a block reduction read back this many waves at a time (block_sum's CHUNK)
+constexpr int ROWS_GATHER = 2;      // staged forward: two at a time (78 -> 62 us; all at once: 88 us, register cliff)
+constexpr int ROWS_G_FWD = 2;       // LayerNorm-only forward: two at a time (40 -> 30.5 us; all at once 33 us)
+constexpr int ROWS_G_BWDS = 16;     // staged backward: all at once (160 -> 134 us); the LayerNorm-only / generic backward keep the plain loop
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-#ifndef ROWS_G_NT
-#define ROWS_G_NT 1        // generic forward body: nontemporal fp32 row loads (LayerNorm 2 reads the residual stream once: encoder forward -0.25 %)
-#endif
+// Nontemporal fp32 row loads of the generic and wave-per-row forward bodies (LayerNorm 2 reads the residual stream once: encoder
+// forward -0.25 %).  The same on the backward bodies' h_in / d_y / g_res loads measured no better (profiles/r03_cache_policy.txt).
 typedef __attribute__((ext_vector_type(4))) float f32x4n_t;
 __device__ __forceinline__ float4 ld4_nt(const float* p) {
     const f32x4n_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4n_t*>(p));
     return make_float4(v.x, v.y, v.z, v.w);
 }
-#ifndef ROWS_GB_NT
-#define ROWS_GB_NT 0       // generic backward body: nontemporal h_in / d_y / g_res loads
-#endif
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2r_t;
-__device__ __forceinline__ float4 ld4_bf16_nt(const void* base, int64_t idx) {
-    const u32x2r_t u = __builtin_nontemporal_load(reinterpret_cast<const u32x2r_t*>(reinterpret_cast<const unsigned short*>(base) + idx));
-    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u),
-                       __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-}
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float4 ld4_bf16(const void* base, int64_t idx) {
     uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + idx);
@@ -215,7 +197,7 @@ __global__ void __launch_bounds__(MAXT) fddt_ln_fwd_kernel(const dicow_fddt_ln_f
             const bool ok = act && row < a.rows;
             const int64_t off = (int64_t)row * D + col;
             x[r] = zero;
-            if (ok) x[r] = a.in_bf16 ? ld4_bf16(a.h_in, off) : (ROWS_G_NT ? ld4_nt(reinterpret_cast<const float*>(a.h_in) + off) : ld4(reinterpret_cast<const float*>(a.h_in) + off));
+            if (ok) x[r] = a.in_bf16 ? ld4_bf16(a.h_in, off) : ld4_nt(reinterpret_cast<const float*>(a.h_in) + off);
             if (mode != 0 && row < a.rows) {
                 const int bi = row / a.T, t = row - bi * a.T;
                 const float* mp = a.stno + (int64_t)bi * a.stno_bstride + t;
@@ -251,7 +233,7 @@ __global__ void __launch_bounds__(MAXT) fddt_ln_fwd_kernel(const dicow_fddt_ln_f
 #pragma unroll
         for (int r = 0; r < R; ++r) sm[r] = act ? (x[r].x + x[r].y) + (x[r].z + x[r].w) : 0.f;
         // (unrolled read-back of the partials: LayerNorm-only body 40 -> 32 us; the FDDT bodies lose occupancy to its registers)
-        block_sum<R, (MODE_T == 0 && ROWS_G_FWD != 0), (ROWS_G_FWD ? ROWS_G_FWD : 16)>(sm, red[0], nwaves);
+        block_sum<R, MODE_T == 0, ROWS_G_FWD>(sm, red[0], nwaves);
         float mu[R], q[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -259,7 +241,7 @@ __global__ void __launch_bounds__(MAXT) fddt_ln_fwd_kernel(const dicow_fddt_ln_f
             const float dx = x[r].x - mu[r], dy = x[r].y - mu[r], dz = x[r].z - mu[r], dw = x[r].w - mu[r];
             q[r] = act ? (dx * dx + dy * dy) + (dz * dz + dw * dw) : 0.f;
         }
-        block_sum<R, (MODE_T == 0 && ROWS_G_FWD != 0), (ROWS_G_FWD ? ROWS_G_FWD : 16)>(q, red[1], nwaves);
+        block_sum<R, MODE_T == 0, ROWS_G_FWD>(q, red[1], nwaves);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int row = row0 + r;
@@ -290,15 +272,7 @@ __global__ void __launch_bounds__(MAXT) fddt_ln_fwd_kernel(const dicow_fddt_ln_f
 // the float4 at columns 4 l + 256 k, k < NC (D = 256 NC: 1280 -> 5), both statistics are DPP reductions inside the wave -- no LDS,
 // no barrier, nothing shared between the waves of a workgroup -- and the affine vectors live in registers (2 x 4 NC).  R rows are
 // requested together.  Same two-pass arithmetic (mean, then centred sum of squares) as the block form.
-#ifndef LNW_ON
-#define LNW_ON 1
-#endif
-#ifndef LNW_R
-#define LNW_R 2
-#endif
-#ifndef LNW_WAVES
-#define LNW_WAVES 8       // (4 or 8 waves per workgroup, 1 / 2 / 4 rows per request group: equal within 0.1 % of the encoder forward)
-#endif
+constexpr int LNW_R = 2, LNW_WAVES = 8;      // (4 or 8 waves per workgroup, 1 / 2 / 4 rows per request group: equal within 0.1 % of the encoder forward)
 template <int NC>
 __global__ void __launch_bounds__(LNW_WAVES * 64) ln_fwd_wave_kernel(const dicow_fddt_ln_fwd_args a) {
     constexpr int R = LNW_R;
@@ -316,7 +290,7 @@ __global__ void __launch_bounds__(LNW_WAVES * 64) ln_fwd_wave_kernel(const dicow
         for (int r = 0; r < R; ++r) {
             const int row = row0 + r < a.rows ? row0 + r : a.rows - 1;
 #pragma unroll
-            for (int k = 0; k < NC; ++k) x[r][k] = ROWS_G_NT ? ld4_nt(H + (int64_t)row * D + 4 * lane + 256 * k) : ld4(H + (int64_t)row * D + 4 * lane + 256 * k);
+            for (int k = 0; k < NC; ++k) x[r][k] = ld4_nt(H + (int64_t)row * D + 4 * lane + 256 * k);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -352,41 +326,30 @@ __global__ void __launch_bounds__(LNW_WAVES * 64) ln_fwd_wave_kernel(const dicow
     }
 }
 
-// FDDT(diag) + LayerNorm forward of every encoder layer in the same wave-per-row form: the eight FDDT vectors (4 classes x weight,
-// bias) and the two LayerNorm affine vectors (10 x 4 D bytes = 50 KiB at D = 1280) live in LDS, written once per workgroup -- the only barrier of the kernel -- and read
-// back as conflict-free 16-byte fragments (10 x NC ds_read_b128 per row and lane against NC 16-byte HBM loads and 3 NC stores).
-// The FDDT arithmetic is the reference's evaluation order (fddt_diag_pair: packed
-// IEEE multiplies / adds, no contraction), bit-exact like the other bodies.  fp32 rows leave in 8-byte stores (see the note on
-// 16-byte stores in the staged kernel).
-#ifndef FLW_R
-#define FLW_R 1
-#endif
-#ifndef FLW_WAVES
-#define FLW_WAVES 8
-#endif
-#ifndef FLW_ON
-#define FLW_ON 0        // measured equal to the LDS-staged column-owner kernel (62-68 against 64.5 us in isolation, encoder forward +-0.1 ms over
-#endif                  // 1 / 2 rows x 4 / 8 / 16 waves: profiles/r03_rows_wave.txt): that kernel is not bound by its barriers; kept for A/B builds
-#ifndef FLW_INIT_ON
-#define FLW_INIT_ON 1
-#endif
-#ifndef FLW_MINWG
-#define FLW_MINWG 2       // resident workgroups per CU the register budget is cut for (8 waves each: 128 VGPRs)
-#endif
-template <int NC, bool INIT = false>      // INIT: the encoder's initial FDDT -- bf16 rows in, + positions, fp32 rows out, no LayerNorm
+// The encoder's initial FDDT(diag) + positions (bf16 rows in, fp32 rows out, no LayerNorm) in the same wave-per-row form: the eight
+// FDDT vectors (4 classes x weight, bias: 8 x 4 D bytes = 40 KiB at D = 1280) live in LDS, written once per workgroup -- the only
+// barrier of the kernel -- and read back as conflict-free 16-byte fragments (8 x NC ds_read_b128 per row and lane).  The FDDT
+// arithmetic is the reference's evaluation order (fddt_diag_pair: packed IEEE multiplies / adds, no contraction), bit-exact like the
+// other bodies.  fp32 rows leave in 8-byte stores (see the note on 16-byte stores in the staged kernel).
+// (The FDDT + LayerNorm of the encoder layers in this form measured equal to the LDS-staged column-owner kernel below -- 62-68 against
+// 64.5 us in isolation, encoder forward +-0.1 ms over 1 / 2 rows x 4 / 8 / 16 waves, profiles/r03_rows_wave.txt: that kernel is not
+// bound by its barriers -- and is gone.)
+constexpr int FLW_R = 1, FLW_WAVES = 8;
+constexpr int FLW_MINWG = 2;       // resident workgroups per CU the register budget is cut for (8 waves each: 128 VGPRs)
+template <int NC>
 __global__ void __launch_bounds__(FLW_WAVES * 64, FLW_MINWG) fddt_ln_fwd_wave_kernel(const dicow_fddt_ln_fwd_args a) {
     constexpr int R = FLW_R;
-    extern __shared__ __attribute__((aligned(16))) char prm[];        // [10 vectors][D] fp32: w0 b0 w1 b1 w2 b2 w3 b3 ln_w ln_b
+    extern __shared__ __attribute__((aligned(16))) char prm[];        // [8 vectors][D] fp32: w0 b0 w1 b1 w2 b2 w3 b3
     const int lane = threadIdx.x & 63, D = a.D;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (int i = threadIdx.x * 4; i < (INIT ? 8 : 10) * D; i += FLW_WAVES * 64 * 4) {
+    for (int i = threadIdx.x * 4; i < 8 * D; i += FLW_WAVES * 64 * 4) {
         const int v = i / D, c = i - v * D;
+        // (v < 8: the two LayerNorm arms never select.  They stay because the compiler does not see that, and without them the prologue
+        // is other code than the one that was measured)
         const float* src = v == 8 ? a.ln_w : v == 9 ? a.ln_b : (v & 1) ? a.b[v >> 1] : a.w[v >> 1];
         *reinterpret_cast<float4*>(prm + (int64_t)i * 4) = ld4(src + c);
     }
     __syncthreads();
-    const float inv_d = 1.0f / (float)D;
-    const float* H = reinterpret_cast<const float*>(a.h_in);
     const int wave = blockIdx.x * FLW_WAVES + wv, nwaves = gridDim.x * FLW_WAVES;
     for (int row0 = wave * R; row0 < a.rows; row0 += nwaves * R) {
         float4 xi[R][NC];
@@ -395,8 +358,7 @@ __global__ void __launch_bounds__(FLW_WAVES * 64, FLW_MINWG) fddt_ln_fwd_wave_ke
         for (int r = 0; r < R; ++r) {
             const int row = row0 + r < a.rows ? row0 + r : a.rows - 1;
 #pragma unroll
-            for (int k = 0; k < NC; ++k) xi[r][k] = INIT ? ld4_bf16(a.h_in, (int64_t)row * D + 4 * lane + 256 * k)
-                                                         : ROWS_G_NT ? ld4_nt(H + (int64_t)row * D + 4 * lane + 256 * k) : ld4(H + (int64_t)row * D + 4 * lane + 256 * k);
+            for (int k = 0; k < NC; ++k) xi[r][k] = ld4_bf16(a.h_in, (int64_t)row * D + 4 * lane + 256 * k);
             const int bi = row / a.T, t = row - bi * a.T;
             const float* mp = a.stno + (int64_t)bi * a.stno_bstride + t;
 #pragma unroll
@@ -408,7 +370,6 @@ __global__ void __launch_bounds__(FLW_WAVES * 64, FLW_MINWG) fddt_ln_fwd_wave_ke
             float m0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m[r][0]))), m1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m[r][1])));
             float m2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m[r][2]))), m3 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m[r][3])));
             f32x2r_t xl[NC], xh[NC];
-            float sm = 0.f;
 #pragma unroll
             for (int k = 0; k < NC; ++k) {
                 float4 pv[8];
@@ -420,7 +381,7 @@ __global__ void __launch_bounds__(FLW_WAVES * 64, FLW_MINWG) fddt_ln_fwd_wave_ke
                 xh[k] = fddt_diag_pair(f32x2r_t{xi[r][k].z, xi[r][k].w}, FLW_P(0, z, w), FLW_P(1, z, w), FLW_P(2, z, w), FLW_P(3, z, w),
                                        FLW_P(4, z, w), FLW_P(5, z, w), FLW_P(6, z, w), FLW_P(7, z, w), m0, m1, m2, m3);
 #undef FLW_P
-                if constexpr (INIT) {                          // + positions, straight out (separate IEEE adds, as the column-owner body)
+                {                                              // + positions, straight out (separate IEEE adds, as the column-owner body)
 #pragma clang fp contract(off)
                     const int t = row - (row / a.T) * a.T;
                     const float4 pz = ld4(a.pos + (int64_t)t * D + 4 * lane + 256 * k);
@@ -432,35 +393,7 @@ __global__ void __launch_bounds__(FLW_WAVES * 64, FLW_MINWG) fddt_ln_fwd_wave_ke
                         *reinterpret_cast<u32x2r_t*>(a.h_out + off + 2) = u32x2r_t{__float_as_uint(xh[k].x), __float_as_uint(xh[k].y)};
                     }
                 }
-                sm += (xl[k].x + xl[k].y) + (xh[k].x + xh[k].y);
                 asm volatile("" ::: "memory");                // (keeps the parameter fragments of the NC chunks from being read all at once: 32 registers each)
-            }
-            if constexpr (INIT) continue;
-            const float mu = wave_sum_dpp(sm) * inv_d;
-            float q = 0.f;
-#pragma unroll
-            for (int k = 0; k < NC; ++k) {
-#pragma clang fp contract(off)
-                const f32x2r_t mu2 = {mu, mu};
-                const f32x2r_t dl = xl[k] - mu2, dh = xh[k] - mu2;
-                const f32x2r_t ql = dl * dl, qh = dh * dh;
-                q += (ql.x + ql.y) + (qh.x + qh.y);
-            }
-            const float rs = rsqrtf(wave_sum_dpp(q) * inv_d + a.eps);
-            if (row >= a.rows) continue;                      // (wave-uniform)
-            if (lane == 0) { a.mean[row] = mu; a.rstd[row] = rs; }
-#pragma unroll
-            for (int k = 0; k < NC; ++k) {
-#pragma clang fp contract(off)
-                const int64_t off = (int64_t)row * D + 4 * lane + 256 * k;
-                *reinterpret_cast<u32x2r_t*>(a.h_out + off) = u32x2r_t{__float_as_uint(xl[k].x), __float_as_uint(xl[k].y)};
-                *reinterpret_cast<u32x2r_t*>(a.h_out + off + 2) = u32x2r_t{__float_as_uint(xh[k].x), __float_as_uint(xh[k].y)};
-                const float4 lw = *reinterpret_cast<const float4*>(prm + ((int64_t)8 * D + 4 * lane + 256 * k) * 4);
-                const float4 lb = *reinterpret_cast<const float4*>(prm + ((int64_t)9 * D + 4 * lane + 256 * k) * 4);
-                const f32x2r_t mu2 = {mu, mu}, rs2 = {rs, rs};
-                const f32x2r_t yl = (xl[k] - mu2) * rs2 * f32x2r_t{lw.x, lw.y} + f32x2r_t{lb.x, lb.y};
-                const f32x2r_t yh = (xh[k] - mu2) * rs2 * f32x2r_t{lw.z, lw.w} + f32x2r_t{lb.z, lb.w};
-                *reinterpret_cast<u32x2r_t*>(reinterpret_cast<unsigned short*>(a.y_bf16) + off) = u32x2r_t{pack_bf16x2(yl.x, yl.y), pack_bf16x2(yh.x, yh.y)};
             }
         }
     }
@@ -471,27 +404,10 @@ __global__ void __launch_bounds__(FLW_WAVES * 64, FLW_MINWG) fddt_ln_fwd_wave_ke
 // next trip fetched by LDS-DMA while the current trip is computed -- see fddt_ln_bwd_staged_kernel for the scheme.  The FDDT
 // arithmetic is the reference's evaluation order (fddt_diag_elem), bit-exact like the generic body.
 typedef __attribute__((address_space(3))) void lds_void_f_t;
-#ifndef ROWS_BWD_H_NT
-#define ROWS_BWD_H_NT 0    // staged backward: cache-policy bits of the h_in / g_res / d_y row requests (each is the last use)
-#endif
-#ifndef ROWS_BWD_G_NT
-#define ROWS_BWD_G_NT 0
-#endif
-#ifndef ROWS_BWD_Y_NT
-#define ROWS_BWD_Y_NT 0
-#endif
-#ifndef ROWS_FWD_ST_NT
-#define ROWS_FWD_ST_NT 0   // ... of its fp32 row stores / its bf16 LayerNorm-output stores
-#endif
-#ifndef ROWS_FWD_Y_NT
-#define ROWS_FWD_Y_NT 0
-#endif
-#ifndef ROWS_FWD_NT
-#define ROWS_FWD_NT 2      // cache-policy bits of the staged forward's row requests (2 = nt: read once; encoder forward -0.25 %)
-#endif
-#ifndef ROWS_ABL
-#define ROWS_ABL 0     // diagnostic builds (tools/build_rows_variants.sh): 1 no fp32 row store, 2 no bf16 / stats stores, 4 no block reductions, 8 no DMA wait
-#endif
+// Cache-policy bits of the staged forward's row requests (2 = nt: read once; encoder forward -0.25 %).  Its fp32 row stores, its bf16
+// LayerNorm-output stores and the staged backward's h_in / g_res / d_y requests keep the default policy: nt on any of them measured
+// nothing (profiles/r03_cache_policy.txt).
+constexpr int ROWS_FWD_NT = 2;
 template <int R>
 __global__ void __launch_bounds__(512) fddt_ln_fwd_staged_kernel(const dicow_fddt_ln_fwd_args a) {
     extern __shared__ __attribute__((aligned(16))) char stg[];       // [2 stages][R rows][4*D bytes]
@@ -542,9 +458,7 @@ __global__ void __launch_bounds__(512) fddt_ln_fwd_staged_kernel(const dicow_fdd
         load_masks(row0 + stride);
         stage_rows(row0 + stride, s ^ 1);
         // younger than this trip's DMA: the previous trip's 4R stores, the next trip's 4R mask loads and R DMA instructions
-        if (ROWS_ABL & 8) asm volatile("s_waitcnt vmcnt(60)" ::: "memory");
-        else if (ROWS_ABL & 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (the store counts changed: wait for everything)
-        else if (it == 0) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(5 * R) : "memory");
+        if (it == 0) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(5 * R) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" :: "i"(9 * R) : "memory");
         f32x2r_t xl[R], xh[R];                       // columns (0,1) and (2,3) of this thread's quad
         float sm[R];
@@ -560,10 +474,10 @@ __global__ void __launch_bounds__(512) fddt_ln_fwd_staged_kernel(const dicow_fdd
             xh[r] = FDP(z, w, (f32x2r_t{xi.z, xi.w}));
 #undef FDP
             ov[r] = u32x4_t{__float_as_uint(xl[r].x), __float_as_uint(xl[r].y), __float_as_uint(xh[r].x), __float_as_uint(xh[r].y)};
-            if (!(ROWS_ABL & 1)) __builtin_amdgcn_raw_buffer_store_b128(ov[r], rsO, vo32, (row0 + r) * D * 4, ROWS_FWD_ST_NT);
+            __builtin_amdgcn_raw_buffer_store_b128(ov[r], rsO, vo32, (row0 + r) * D * 4, 0);
             sm[r] = (xl[r].x + xl[r].y) + (xh[r].x + xh[r].y);
         }
-        if (!(ROWS_ABL & 4)) block_sum<R, ROWS_GATHER != 0, (ROWS_GATHER ? ROWS_GATHER : 16)>(sm, red[0], nwaves);
+        block_sum<R, true, ROWS_GATHER>(sm, red[0], nwaves);
         float mu[R], q[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -574,7 +488,7 @@ __global__ void __launch_bounds__(512) fddt_ln_fwd_staged_kernel(const dicow_fdd
             const f32x2r_t ql = dl * dl, qh = dh * dh;
             q[r] = (ql.x + ql.y) + (qh.x + qh.y);
         }
-        if (!(ROWS_ABL & 4)) block_sum<R, ROWS_GATHER != 0, (ROWS_GATHER ? ROWS_GATHER : 16)>(q, red[1], nwaves);
+        block_sum<R, true, ROWS_GATHER>(q, red[1], nwaves);
         // (one block-wide Chan/Welford reduction instead of these two measured SLOWER here: 108 vs 87 us -- the combination
         // steps cost more than the second barrier)
         // The registers a 16-byte store reads its data from must not be rewritten while the store may still be queued: with
@@ -589,38 +503,102 @@ __global__ void __launch_bounds__(512) fddt_ln_fwd_staged_kernel(const dicow_fdd
 #pragma clang fp contract(off)
             const float rs = rsqrtf(q[r] * inv_d + a.eps);
             typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-            if (!(ROWS_ABL & 2)) {
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mu[r]), rsM, voStat, (row0 + r) * 4, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rs), rsS, voStat, (row0 + r) * 4, 0);
-            }
             const f32x2r_t mu2 = {mu[r], mu[r]}, rs2 = {rs, rs};
             const f32x2r_t yl = (xl[r] - mu2) * rs2 * f32x2r_t{lnw.x, lnw.y} + f32x2r_t{lnb.x, lnb.y};
             const f32x2r_t yh = (xh[r] - mu2) * rs2 * f32x2r_t{lnw.z, lnw.w} + f32x2r_t{lnb.z, lnb.w};
             const u32x2_t yv = {pack_bf16x2(yl.x, yl.y), pack_bf16x2(yh.x, yh.y)};
-            if (!(ROWS_ABL & 2)) __builtin_amdgcn_raw_buffer_store_b64(yv, rsY, vo16, (row0 + r) * D * 2, ROWS_FWD_Y_NT);
-            else if (yv.x == 0x12345678u) __builtin_amdgcn_raw_buffer_store_b64(yv, rsY, vo16, (row0 + r) * D * 2, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(yv, rsY, vo16, (row0 + r) * D * 2, 0);
         }
     }
 }
 
-// resident workgroups per CU for a row kernel (occupancy API, cached): the grid is sized to exactly fill the chip
-// once and every workgroup strides over rows, so no partial tail wave runs at low occupancy.
-template <typename K>
-static int resident_grid(K kernel, int block, int* cache) {
-    int nb = __atomic_load_n(cache, __ATOMIC_RELAXED);      // (any host thread may get here first: the query is idempotent)
-    if (nb == 0) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, 0) != hipSuccess || nb < 1) nb = 1;
-        __atomic_store_n(cache, nb, __ATOMIC_RELAXED);
+// ------------------------------------------------------------------------------------------------ host dispatch
+// rows_fwd_plan / rows_bwd_plan: which body runs a problem, on which workgroup shape.  Host arithmetic on the arguments alone -- no HIP
+// call, no validation -- shared by the dispatchers, the route queries of the ABI and dicow_fddt_ln_bwd_ws_bytes.
+constexpr int ROW_CUS = 256;            // CUs a row kernel's grid is sized for
+constexpr int ASK_OCCUPANCY = 0;        // rows_plan_t::per_cu: no measured count, ask the occupancy API
+constexpr int ROWS_R = 4;               // rows per trip of the forward column-owner bodies; rows per workgroup every column-owner grid is cut for
+
+enum rows_body_t {
+    ROWS_FWD_STAGED,            // fddt_ln_fwd_staged_kernel: FDDT(diag) + LayerNorm of an encoder layer
+    ROWS_FWD_INIT_WAVE,         // fddt_ln_fwd_wave_kernel<NC>: the encoder's initial FDDT(diag) + positions
+    ROWS_FWD_LN_WAVE,           // ln_fwd_wave_kernel<NC>: LayerNorm only
+    ROWS_FWD_GENERIC_LN,        // fddt_ln_fwd_kernel with mode 0 / mode 1 / the mode of the arguments compiled in
+    ROWS_FWD_GENERIC_DIAG,
+    ROWS_FWD_GENERIC,
+    ROWS_FWD_GENERIC_1024,      // ... for D > 2048: 1024-thread workgroups
+    ROWS_BWD_LN_WAVE,           // ln_bwd_wave_kernel<NC>: LayerNorm only
+    ROWS_BWD_STAGED_BF16,       // fddt_ln_bwd_staged_kernel with / without the bf16 copy of g_out
+    ROWS_BWD_STAGED_F32,
+    ROWS_BWD_LN_ONLY,           // fddt_ln_bwd_kernel<.., 0, 1>: LayerNorm only, any width
+    ROWS_BWD_GENERIC,
+    ROWS_BWD_GENERIC_1024
+};
+static const char* const rows_body_name[] = {"staged", "init_wave", "ln_wave", "generic_ln", "generic_diag", "generic", "generic_1024",
+                                             "ln_wave", "staged_bf16", "staged_f32", "ln_only", "generic", "generic_1024"};
+struct rows_plan_t {
+    rows_body_t body;
+    int block;      // threads per workgroup
+    int grid;       // workgroups the rows ask for; the launch caps it to ROW_CUS * per_cu: the grid fills the chip once and every
+                    // workgroup strides over rows, so no partial tail wave runs at low occupancy
+    int lds;        // dynamic LDS bytes
+    int per_cu;     // resident workgroups per CU: a measured count, or ASK_OCCUPANCY
+    int ws_grid;    // backward: partial column-sum rows the caller's workspace must hold
+};
+
+static bool wave_width(int D) { return D % 256 == 0 && D >= 512 && D <= 1280; }       // the wave-per-row kernels: D = 256 NC, NC = 2..5
+static int row_block(int D) { return ((D / 4) + 63) / 64 * 64; }                      // the column-owner bodies: D / 4 threads, whole waves
+template <typename A>
+static bool all_fddt_vectors(const A* a) { return a->w[0] && a->w[1] && a->w[2] && a->w[3] && a->b[0] && a->b[1] && a->b[2] && a->b[3]; }
+
+static rows_plan_t rows_fwd_plan(const dicow_fddt_ln_fwd_args* a) {
+    const int block = row_block(a->D);
+    rows_plan_t p = {ROWS_FWD_GENERIC, block, dicow_cdiv(a->rows, ROWS_R), 0, ASK_OCCUPANCY, 0};
+    if (block <= 512 && block * 4 == a->D && a->mode == 1 && a->ln_w && !a->in_bf16 && a->h_out && a->y_bf16 && !a->y_f32 && a->mean &&
+        a->rstd && !a->pos && all_fddt_vectors(a) && (int64_t)a->rows * a->D * 4 < (1ll << 31)) {       // (32-bit buffer offsets)
+        p.body = ROWS_FWD_STAGED;
+        p.lds = 2 * ROWS_R * 4 * a->D;
+        p.per_cu = 2;                                 // two resident workgroups per CU (a third one measured SLOWER: 90 vs 82 us)
+    } else if (a->mode == 1 && !a->ln_w && a->in_bf16 && a->h_out && a->pos && !a->y_bf16 && !a->y_f32 && wave_width(a->D) && all_fddt_vectors(a)) {
+        // the encoder's initial FDDT(diag) + positions (bf16 rows in, fp32 rows out, no LayerNorm): the wave-per-row form with the eight
+        // vectors in LDS (the column-owner body runs this shape at 1.8 TB/s: scalar FDDT arithmetic at two workgroups per CU)
+        p = {ROWS_FWD_INIT_WAVE, FLW_WAVES * 64, dicow_cdiv(a->rows, FLW_R * FLW_WAVES), 8 * a->D * 4, ASK_OCCUPANCY, 0};
+    } else if (a->mode == 0 && a->ln_w && !a->in_bf16 && !a->h_out && !a->pos && wave_width(a->D) && (a->y_bf16 || a->y_f32)) {
+        // LayerNorm only, fp32 rows of 256 NC columns: a wave per row (no barrier, no LDS)
+        p = {ROWS_FWD_LN_WAVE, LNW_WAVES * 64, dicow_cdiv(a->rows, LNW_R * LNW_WAVES), 0, ASK_OCCUPANCY, 0};
+    } else {
+        p.body = block > 512 ? ROWS_FWD_GENERIC_1024 : a->mode == 0 ? ROWS_FWD_GENERIC_LN : a->mode == 1 ? ROWS_FWD_GENERIC_DIAG : ROWS_FWD_GENERIC;
     }
-    return 256 * nb;
+    return p;
 }
 
-static int pick_block(int D) {
-    int t = ((D / 4) + 63) / 64 * 64;
-    return t;
+// One launch of a row kernel on its plan: the grid capped to the workgroups resident at once.  Where the plan has no measured count
+// the occupancy API is asked once per kernel and workgroup size.  Returns the workgroups launched.
+template <auto kernel, typename A>
+static int launch_rows(const rows_plan_t& p, const A& a, hipStream_t st) {
+    int per_cu = p.per_cu;
+    if (per_cu == ASK_OCCUPANCY) {
+        static int occ[MAX_WAVES + 1] = {0};
+        per_cu = __atomic_load_n(&occ[p.block / 64], __ATOMIC_RELAXED);       // (any host thread may get here first: the query is idempotent)
+        if (per_cu == 0) {
+            if (p.lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, p.block, p.lds) != hipSuccess || per_cu < 1) per_cu = 1;
+            __atomic_store_n(&occ[p.block / 64], per_cu, __ATOMIC_RELAXED);
+        }
+    }
+    const int grid = p.grid < ROW_CUS * per_cu ? p.grid : ROW_CUS * per_cu;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(p.block), p.lds, st, a);
+    return grid;
 }
+// ... of a wave-per-row kernel, a template over NC = D / 256
+#define LAUNCH_WAVE_ROWS(k, p, a, st) ((a).D / 256 == 5 ? launch_rows<k<5>>(p, a, st) : (a).D / 256 == 4 ? launch_rows<k<4>>(p, a, st) : \
+                                       (a).D / 256 == 3 ? launch_rows<k<3>>(p, a, st) : launch_rows<k<2>>(p, a, st))
+#define ROWS_CHECK_LAUNCH(what, p) do { hipError_t e_ = hipGetLastError(); \
+    if (e_ != hipSuccess) DICOW_FAIL(DICOW_ERR_LAUNCH, what " (%s): %s", rows_body_name[(p).body], hipGetErrorString(e_)); } while (0)
 
-extern "C" int dicow_fddt_ln_fwd(const dicow_fddt_ln_fwd_args* a, void* stream) {
+static int rows_fwd_validate(const dicow_fddt_ln_fwd_args* a) {
     DICOW_REQUIRE(a && a->h_in && a->rows > 0 && a->D > 0, "fddt_ln_fwd: null/empty input");
     DICOW_REQUIRE(a->D % 4 == 0 && a->D <= 4096, "fddt_ln_fwd: D=%d must be a multiple of 4 and <= 4096", a->D);
     DICOW_REQUIRE(a->mode >= 0 && a->mode <= 2, "fddt_ln_fwd: bad mode %d", a->mode);
@@ -628,130 +606,35 @@ extern "C" int dicow_fddt_ln_fwd(const dicow_fddt_ln_fwd_args* a, void* stream) 
     DICOW_REQUIRE(a->pos == nullptr || a->T > 0, "fddt_ln_fwd: pos needs T");
     DICOW_REQUIRE((a->ln_w == nullptr) == (a->ln_b == nullptr), "fddt_ln_fwd: ln_w/ln_b must both be given");
     DICOW_REQUIRE(a->ln_w || a->h_out, "fddt_ln_fwd: nothing to write");
-    const int R = 4;
-    const int block = pick_block(a->D);
-    int grid = dicow_cdiv(a->rows, R);
-#ifdef DICOW_ABLATIONS
-    static const int fwd_env = getenv("DICOW_ROW_FWD") ? atoi(getenv("DICOW_ROW_FWD")) : 0;      // 9: generic body (diagnostic builds only)
-#else
-    constexpr int fwd_env = 0;
-#endif
-    const bool staged = fwd_env != 9 && block <= 512 && block * 4 == a->D && a->mode == 1 && a->ln_w && !a->in_bf16 && a->h_out &&
-                        a->y_bf16 && !a->y_f32 && a->mean && a->rstd && !a->pos && a->w[0] && a->w[1] && a->w[2] && a->w[3] &&
-                        a->b[0] && a->b[1] && a->b[2] && a->b[3] && (int64_t)a->rows * a->D * 4 < (1ll << 31);
-    if (staged && FLW_ON && fwd_env == 0 && a->D % 256 == 0 && a->D >= 512 && a->D <= 1280) {
-        const int nc = a->D / 256;
-        const int lds = 10 * a->D * 4;
-        const void* fn = nc == 5 ? (const void*)fddt_ln_fwd_wave_kernel<5> : nc == 4 ? (const void*)fddt_ln_fwd_wave_kernel<4>
-                       : nc == 3 ? (const void*)fddt_ln_fwd_wave_kernel<3> : (const void*)fddt_ln_fwd_wave_kernel<2>;
-        static int occf[6] = {0};
-        int per_cu = __atomic_load_n(&occf[nc], __ATOMIC_RELAXED);
-        if (per_cu == 0) {
-            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, FLW_WAVES * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-            __atomic_store_n(&occf[nc], per_cu, __ATOMIC_RELAXED);
-        }
-        int gw = dicow_cdiv(a->rows, FLW_R * FLW_WAVES);
-        if (gw > 256 * per_cu) gw = 256 * per_cu;
-        switch (nc) {
-            case 5: hipLaunchKernelGGL(fddt_ln_fwd_wave_kernel<5>, dim3(gw), dim3(FLW_WAVES * 64), lds, (hipStream_t)stream, *a); break;
-            case 4: hipLaunchKernelGGL(fddt_ln_fwd_wave_kernel<4>, dim3(gw), dim3(FLW_WAVES * 64), lds, (hipStream_t)stream, *a); break;
-            case 3: hipLaunchKernelGGL(fddt_ln_fwd_wave_kernel<3>, dim3(gw), dim3(FLW_WAVES * 64), lds, (hipStream_t)stream, *a); break;
-            default: hipLaunchKernelGGL(fddt_ln_fwd_wave_kernel<2>, dim3(gw), dim3(FLW_WAVES * 64), lds, (hipStream_t)stream, *a); break;
-        }
-        DICOW_CHECK_LAUNCH("fddt_ln_fwd_wave");
-        return DICOW_OK;
+    return DICOW_OK;
+}
+
+extern "C" const char* dicow_fddt_ln_fwd_route(const dicow_fddt_ln_fwd_args* a) {
+    return rows_fwd_validate(a) == DICOW_OK ? rows_body_name[rows_fwd_plan(a).body] : nullptr;
+}
+
+extern "C" int dicow_fddt_ln_fwd(const dicow_fddt_ln_fwd_args* a, void* stream) {
+    if (const int rc = rows_fwd_validate(a)) return rc;
+    const rows_plan_t p = rows_fwd_plan(a);
+    const hipStream_t st = (hipStream_t)stream;
+    // (here and in the backward the cases name the kernels in the order the code object has always held them: the order of first use is
+    // the order of instantiation, and profiles/r07_nt_dispatch_refactor_ab.txt records a step that moved with kernel placement alone)
+    switch (p.body) {
+        case ROWS_FWD_STAGED: {
+            static const bool attr = [] {
+                (void)hipFuncSetAttribute((const void*)fddt_ln_fwd_staged_kernel<ROWS_R>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ROWS_R * 4 * 2048);
+                return true; }();
+            (void)attr;
+            launch_rows<fddt_ln_fwd_staged_kernel<ROWS_R>>(p, *a, st);
+        } break;
+        case ROWS_FWD_INIT_WAVE: LAUNCH_WAVE_ROWS(fddt_ln_fwd_wave_kernel, p, *a, st); break;
+        case ROWS_FWD_LN_WAVE: LAUNCH_WAVE_ROWS(ln_fwd_wave_kernel, p, *a, st); break;
+        case ROWS_FWD_GENERIC_1024: launch_rows<fddt_ln_fwd_kernel<ROWS_R, 1024>>(p, *a, st); break;
+        case ROWS_FWD_GENERIC_LN: launch_rows<fddt_ln_fwd_kernel<ROWS_R, 512, 0>>(p, *a, st); break;
+        case ROWS_FWD_GENERIC_DIAG: launch_rows<fddt_ln_fwd_kernel<ROWS_R, 512, 1>>(p, *a, st); break;
+        default: launch_rows<fddt_ln_fwd_kernel<ROWS_R, 512>>(p, *a, st); break;
     }
-    if (staged) {
-        static const bool attr = [] {
-            (void)hipFuncSetAttribute((const void*)fddt_ln_fwd_staged_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * 4 * 2048);
-#ifdef DICOW_ABLATIONS
-            (void)hipFuncSetAttribute((const void*)fddt_ln_fwd_staged_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 4 * 2048);
-#endif
-            return true; }();
-        (void)attr;
-        int cap = 256 * 2;                            // two resident workgroups per CU (a third one measured SLOWER: 90 vs 82 us)
-#ifdef DICOW_ABLATIONS
-        const int Rv = getenv("DICOW_ROW_R") ? atoi(getenv("DICOW_ROW_R")) : 4;
-        if (getenv("DICOW_ROW_CAP")) cap = 256 * atoi(getenv("DICOW_ROW_CAP"));
-        if (Rv != 4) {
-            grid = dicow_cdiv(a->rows, Rv); if (grid > cap) grid = cap;
-            hipLaunchKernelGGL((fddt_ln_fwd_staged_kernel<2>), dim3(grid), dim3(block), 2 * 2 * 4 * a->D, (hipStream_t)stream, *a);
-            DICOW_CHECK_LAUNCH("fddt_ln_fwd_staged");
-            return DICOW_OK;
-        }
-#endif
-        if (grid > cap) grid = cap;
-        hipLaunchKernelGGL((fddt_ln_fwd_staged_kernel<4>), dim3(grid), dim3(block), 2 * R * 4 * a->D, (hipStream_t)stream, *a);
-        DICOW_CHECK_LAUNCH("fddt_ln_fwd_staged");
-        return DICOW_OK;
-    }
-    // the encoder's initial FDDT(diag) + positions (bf16 rows in, fp32 rows out, no LayerNorm): the wave-per-row form with the eight
-    // vectors in LDS (the column-owner body runs this shape at 1.8 TB/s: scalar FDDT arithmetic at two workgroups per CU)
-    if (FLW_INIT_ON && a->mode == 1 && !a->ln_w && a->in_bf16 && a->h_out && a->pos && !a->y_bf16 && !a->y_f32 && a->D % 256 == 0 &&
-        a->D >= 512 && a->D <= 1280 && a->w[0] && a->w[1] && a->w[2] && a->w[3] && a->b[0] && a->b[1] && a->b[2] && a->b[3]) {
-        const int nc = a->D / 256;
-        const int lds = 8 * a->D * 4;
-        const void* fn = nc == 5 ? (const void*)fddt_ln_fwd_wave_kernel<5, true> : nc == 4 ? (const void*)fddt_ln_fwd_wave_kernel<4, true>
-                       : nc == 3 ? (const void*)fddt_ln_fwd_wave_kernel<3, true> : (const void*)fddt_ln_fwd_wave_kernel<2, true>;
-        static int occi[6] = {0};
-        int per_cu = __atomic_load_n(&occi[nc], __ATOMIC_RELAXED);
-        if (per_cu == 0) {
-            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, FLW_WAVES * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-            __atomic_store_n(&occi[nc], per_cu, __ATOMIC_RELAXED);
-        }
-        int gw = dicow_cdiv(a->rows, FLW_R * FLW_WAVES);
-        if (gw > 256 * per_cu) gw = 256 * per_cu;
-        switch (nc) {
-            case 5: hipLaunchKernelGGL((fddt_ln_fwd_wave_kernel<5, true>), dim3(gw), dim3(FLW_WAVES * 64), lds, (hipStream_t)stream, *a); break;
-            case 4: hipLaunchKernelGGL((fddt_ln_fwd_wave_kernel<4, true>), dim3(gw), dim3(FLW_WAVES * 64), lds, (hipStream_t)stream, *a); break;
-            case 3: hipLaunchKernelGGL((fddt_ln_fwd_wave_kernel<3, true>), dim3(gw), dim3(FLW_WAVES * 64), lds, (hipStream_t)stream, *a); break;
-            default: hipLaunchKernelGGL((fddt_ln_fwd_wave_kernel<2, true>), dim3(gw), dim3(FLW_WAVES * 64), lds, (hipStream_t)stream, *a); break;
-        }
-        DICOW_CHECK_LAUNCH("fddt_fwd_wave_init");
-        return DICOW_OK;
-    }
-    // LayerNorm only, fp32 rows of 256 NC columns: a wave per row (no barrier, no LDS)
-    if (LNW_ON && a->mode == 0 && a->ln_w && !a->in_bf16 && !a->h_out && !a->pos && a->D % 256 == 0 && a->D >= 512 && a->D <= 1280 &&
-        (a->y_bf16 || a->y_f32)) {
-        static int occw[6] = {0};
-        const int nc = a->D / 256;
-        int per_cu = __atomic_load_n(&occw[nc], __ATOMIC_RELAXED);
-        if (per_cu == 0) {
-            const void* fn = nc == 5 ? (const void*)ln_fwd_wave_kernel<5> : nc == 4 ? (const void*)ln_fwd_wave_kernel<4>
-                           : nc == 3 ? (const void*)ln_fwd_wave_kernel<3> : (const void*)ln_fwd_wave_kernel<2>;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, LNW_WAVES * 64, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-            __atomic_store_n(&occw[nc], per_cu, __ATOMIC_RELAXED);
-        }
-        int gw = dicow_cdiv(a->rows, LNW_R * LNW_WAVES);
-        const int capw = 256 * per_cu;
-        if (gw > capw) gw = capw;
-        switch (nc) {
-            case 5: hipLaunchKernelGGL(ln_fwd_wave_kernel<5>, dim3(gw), dim3(LNW_WAVES * 64), 0, (hipStream_t)stream, *a); break;
-            case 4: hipLaunchKernelGGL(ln_fwd_wave_kernel<4>, dim3(gw), dim3(LNW_WAVES * 64), 0, (hipStream_t)stream, *a); break;
-            case 3: hipLaunchKernelGGL(ln_fwd_wave_kernel<3>, dim3(gw), dim3(LNW_WAVES * 64), 0, (hipStream_t)stream, *a); break;
-            default: hipLaunchKernelGGL(ln_fwd_wave_kernel<2>, dim3(gw), dim3(LNW_WAVES * 64), 0, (hipStream_t)stream, *a); break;
-        }
-        DICOW_CHECK_LAUNCH("ln_fwd_wave");
-        return DICOW_OK;
-    }
-    static int occ[4][17] = {{0}};
-    const int variant = block > 512 ? 2 : (a->mode == 0 ? 1 : a->mode == 1 ? 3 : 0);
-    const int cap = variant == 2 ? resident_grid(fddt_ln_fwd_kernel<R, 1024>, block, &occ[2][block / 64])
-                  : variant == 1 ? resident_grid(fddt_ln_fwd_kernel<R, 512, 0>, block, &occ[1][block / 64])
-                  : variant == 3 ? resident_grid(fddt_ln_fwd_kernel<R, 512, 1>, block, &occ[3][block / 64])
-                                 : resident_grid(fddt_ln_fwd_kernel<R, 512>, block, &occ[0][block / 64]);
-    if (grid > cap) grid = cap;
-    if (variant == 2)
-        hipLaunchKernelGGL((fddt_ln_fwd_kernel<R, 1024>), dim3(grid), dim3(block), 0, (hipStream_t)stream, *a);
-    else if (variant == 1)
-        hipLaunchKernelGGL((fddt_ln_fwd_kernel<R, 512, 0>), dim3(grid), dim3(block), 0, (hipStream_t)stream, *a);
-    else if (variant == 3)
-        hipLaunchKernelGGL((fddt_ln_fwd_kernel<R, 512, 1>), dim3(grid), dim3(block), 0, (hipStream_t)stream, *a);
-    else
-        hipLaunchKernelGGL((fddt_ln_fwd_kernel<R, 512>), dim3(grid), dim3(block), 0, (hipStream_t)stream, *a);
-    DICOW_CHECK_LAUNCH("fddt_ln_fwd");
+    ROWS_CHECK_LAUNCH("fddt_ln_fwd", p);
     return DICOW_OK;
 }
 
@@ -799,9 +682,9 @@ __global__ void __launch_bounds__(MAXT) fddt_ln_bwd_kernel(const dicow_fddt_ln_b
             const int64_t off = (int64_t)row * D + col;
             hin[r] = zero; dy[r] = zero; rs[r] = 0.f;
             float mu = 0.f;
-            if (ok) hin[r] = a.in_bf16 ? ld4_bf16(a.h_in, off) : ROWS_GB_NT ? ld4_nt(reinterpret_cast<const float*>(a.h_in) + off) : ld4(reinterpret_cast<const float*>(a.h_in) + off);
-            if (ok && do_ln) dy[r] = a.dy_f32 ? ld4(reinterpret_cast<const float*>(a.d_y) + off) : ROWS_GB_NT ? ld4_bf16_nt(a.d_y, off) : ld4_bf16(a.d_y, off);
-            gr[r] = (ok && a.g_res) ? (ROWS_GB_NT ? ld4_nt(a.g_res + off) : ld4(a.g_res + off)) : zero;      // issued with the other loads, ahead of the reduction
+            if (ok) hin[r] = a.in_bf16 ? ld4_bf16(a.h_in, off) : ld4(reinterpret_cast<const float*>(a.h_in) + off);
+            if (ok && do_ln) dy[r] = a.dy_f32 ? ld4(reinterpret_cast<const float*>(a.d_y) + off) : ld4_bf16(a.d_y, off);
+            gr[r] = (ok && a.g_res) ? ld4(a.g_res + off) : zero;      // issued with the other loads, ahead of the reduction
             if (do_ln && row < a.rows) { mu = a.mean[row]; rs[r] = a.rstd[row]; }
             if (mode != 0 && row < a.rows) {
                 const int bi = row / a.T, t = row - bi * a.T;
@@ -846,7 +729,7 @@ __global__ void __launch_bounds__(MAXT) fddt_ln_bwd_kernel(const dicow_fddt_ln_b
             sums[2 * r] = ok ? (dxh.x + dxh.y) + (dxh.z + dxh.w) : 0.f;
             sums[2 * r + 1] = ok ? (dxh.x * xh[r].x + dxh.y * xh[r].y) + (dxh.z * xh[r].z + dxh.w * xh[r].w) : 0.f;
         }
-        if (do_ln) block_sum<2 * R, ROWS_G_BWD != 0, (ROWS_G_BWD ? ROWS_G_BWD : 16)>(sums, red[it & 1], nwaves);
+        if (do_ln) block_sum<2 * R>(sums, red[it & 1], nwaves);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int row = row0 + r;
@@ -909,7 +792,7 @@ __global__ void __launch_bounds__(MAXT) fddt_ln_bwd_kernel(const dicow_fddt_ln_b
 typedef __attribute__((address_space(3))) void lds_void_t;
 template <int R, bool OUT_BF16>
 __global__ void __launch_bounds__(512) fddt_ln_bwd_staged_kernel(const dicow_fddt_ln_bwd_args a) {
-    extern __shared__ __attribute__((aligned(16))) char stg[];       // [2 or 3 stages][R rows][10*D bytes]: h_in | g_res | d_y
+    extern __shared__ __attribute__((aligned(16))) char stg[];       // [2 stages][R rows][10*D bytes]: h_in | g_res | d_y
     __shared__ float red[2][MAX_WAVES * 2 * R];
     const int tid = threadIdx.x, lane = tid & 63, col = tid * 4, D = a.D;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -939,10 +822,10 @@ __global__ void __launch_bounds__(512) fddt_ln_bwd_staged_kernel(const dicow_fdd
             char* base = stg + (s * R + r) * row_lds;
             const int so32 = (row0 + r) * D * 4, so16 = (row0 + r) * D * 2;
             // (assembly-issued, common.h dicow_dma16: the compiler's own LDS-DMA made it wait for the NEWEST request at every trip's first LDS read)
-            dicow_dma16<ROWS_BWD_H_NT>((unsigned)(uintptr_t)(base + wave * 1024), rsH, vo32, (unsigned)so32);
-            dicow_dma16<ROWS_BWD_G_NT>((unsigned)(uintptr_t)(base + 4 * D + wave * 1024), rsG, vo32, (unsigned)so32);
+            dicow_dma16<0>((unsigned)(uintptr_t)(base + wave * 1024), rsH, vo32, (unsigned)so32);
+            dicow_dma16<0>((unsigned)(uintptr_t)(base + 4 * D + wave * 1024), rsG, vo32, (unsigned)so32);
             if (lane < 32 && (int)voY < 2 * D)       // (a last, partly filled wave: only the lanes inside the row)
-                dicow_dma16<ROWS_BWD_Y_NT>((unsigned)(uintptr_t)(base + 8 * D + wave * 512), rsY, voY, (unsigned)so16);
+                dicow_dma16<0>((unsigned)(uintptr_t)(base + 8 * D + wave * 512), rsY, voY, (unsigned)so16);
         }
     };
     // per-row scalars (mean, rstd, 4 STNO masks) of a trip are ordinary loads: they are requested one trip ahead, BEFORE
@@ -961,14 +844,9 @@ __global__ void __launch_bounds__(512) fddt_ln_bwd_staged_kernel(const dicow_fdd
     };
     const int stride = gridDim.x * R;
     int row0 = blockIdx.x * R, it = 0;
-#if BWD_DEPTH == 2
-    // Three LDS stages, the row DMA runs TWO trips ahead (the per-row scalars one): with one trip in flight a CU holds 38 KB
-    // of requests, ~19 GB/s per CU at the loaded HBM latency -- 4.9 TB/s chip-wide at best, 3.9 measured; two trips hold 77 KB.
-    if (row0 < a.rows) { load_scalars(row0); stage_rows(row0, 0); stage_rows(row0 + stride, 1); }
-    int sg = 0;                                                      // LDS stage of the trip being computed
-#else
+    // (the row DMA runs ONE trip ahead, two LDS stages.  Two trips ahead on three stages measured equal, 124-126 us either way:
+    // the barrier of the per-trip block reduction is the limit, not the DMA latency -- profiles/r03_rows_depth.txt, r06_rows.txt)
     if (row0 < a.rows) { load_scalars(row0); stage_rows(row0, 0); }
-#endif
     // Store data lives in these quads until the NEXT trip's reduction is over: rewriting the registers of a queued 16-byte store
     // (the compiler reused its temporaries at once) corrupted ~1 % of g_out at D = 1280, exactly as in the staged forward.
     typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
@@ -978,31 +856,17 @@ __global__ void __launch_bounds__(512) fddt_ln_bwd_staged_kernel(const dicow_fdd
 #pragma unroll
     for (int r = 0; r < R; ++r) { ov[r] = u32x4_t{0, 0, 0, 0}; bv[r] = u32x2_t{0, 0}; }
     for (; row0 < a.rows; row0 += stride, ++it) {
-#if BWD_DEPTH == 2
-        const int s = sg;
-        const int s2 = sg == 0 ? 2 : sg - 1;                         // (sg + 2) % 3: the stage trip t-1 has finished reading
-        sg = sg == 2 ? 0 : sg + 1;
-#else
         const int s = it & 1;
-#endif
         float sc[R][6];
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
             for (int c = 0; c < 6; ++c) sc[r][c] = sc_n[r][c];
         load_scalars(row0 + stride);
-#if BWD_DEPTH == 2
-        stage_rows(row0 + 2 * stride, s2);                           // (past the end: out-of-range rows read as zero)
-        // issue order: ... S(t) D(t+1) | stores(t-1) | S(t+1) D(t+2) | this wait.  Needed: D(t) (older) and S(t); younger than
-        // S(t): D(t+1) 3R, the previous trip's stores, S(t+1) 6R, D(t+2) 3R.  First trip: S(0) D(0) D(1) | S(1) D(2).
-        if (it == 0) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(12 * R) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" :: "i"((OUT_BF16 ? 14 : 13) * R) : "memory");
-#else
         stage_rows(row0 + stride, s ^ 1);                            // (past the end: out-of-range rows read as zero)
         // younger than this trip's DMA: the previous trip's stores, the scalars and the DMA just issued -- fixed counts
         if (it == 0) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(9 * R) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" :: "i"((OUT_BF16 ? 11 : 10) * R) : "memory");
-#endif
         float4 hin[R], xh[R], dy[R], scw[R];
         float m[R][4], rs[R], sums[2 * R];
 #pragma unroll
@@ -1033,7 +897,7 @@ __global__ void __launch_bounds__(512) fddt_ln_bwd_staged_kernel(const dicow_fdd
             sums[2 * r] = (dxh.x + dxh.y) + (dxh.z + dxh.w);
             sums[2 * r + 1] = (dxh.x * xh[r].x + dxh.y * xh[r].y) + (dxh.z * xh[r].z + dxh.w * xh[r].w);
         }
-        if (!(ROWS_ABL & 16)) block_sum<2 * R, ROWS_G_BWDS != 0, (ROWS_G_BWDS ? ROWS_G_BWDS : 16)>(sums, red[it & 1], nwaves);    // (160 -> 134 us)
+        block_sum<2 * R, true, ROWS_G_BWDS>(sums, red[it & 1], nwaves);
 #pragma unroll
         for (int r = 0; r < R; ++r) { asm volatile("" :: "v"(ov[r])); if (OUT_BF16) asm volatile("" :: "v"(bv[r])); }
 #pragma unroll
@@ -1083,15 +947,7 @@ __global__ void __launch_bounds__(512) fddt_ln_bwd_staged_kernel(const dicow_fdd
 // the three column sums (d ln_w, d ln_b, the bias gradient of the producing Linear) accumulate in 3 x 4 NC registers per lane.  They
 // meet once, at the end, in LDS (wave after wave, in order: deterministic) and leave as this workgroup's row of the same
 // [workgroup][11][D] workspace the column-owner bodies write.  Same arithmetic per element as fddt_ln_bwd_kernel.
-#ifndef LBW_ON
-#define LBW_ON 1
-#endif
-#ifndef LBW_WAVES
-#define LBW_WAVES 8
-#endif
-#ifndef LBW_MINWG
-#define LBW_MINWG 1
-#endif
+constexpr int LBW_WAVES = 8, LBW_MINWG = 1;
 template <int NC>
 __global__ void __launch_bounds__(LBW_WAVES * 64, LBW_MINWG) ln_bwd_wave_kernel(const dicow_fddt_ln_bwd_args a) {
     extern __shared__ __attribute__((aligned(16))) char csum[];       // [3][D] fp32
@@ -1167,56 +1023,67 @@ __global__ void __launch_bounds__(LBW_WAVES * 64, LBW_MINWG) ln_bwd_wave_kernel(
     }
 }
 
-#ifndef BWD_DEPTH
-#define BWD_DEPTH 1       // row DMA trips in flight in the staged backward (1: two LDS stages, 2: three -- measured equal: 124-126 us
-                          // either way, profiles/r03_rows_depth.txt; the barrier of the per-trip block reduction is the limit, not the DMA latency)
-#endif
-#ifndef BWD_R0
-#define BWD_R0 2          // rows per trip and resident workgroups per CU of the LayerNorm-only (mode 0) body
-#endif
-#ifndef BWD_CU0
-#define BWD_CU0 4
-#endif
-#ifndef BWD_RS
-#define BWD_RS 3          // rows per trip / resident workgroups per CU of the LDS-staged FDDT(diag)+LN body: 3 rows x 1 workgroup
-#endif                    // measured 126 us, 2 x 2: 137, 4 x 1: 128, 3 x 2: 131, 2 x 1: 129 (one block reduction per trip: 32 us of it)
-#ifndef BWD_CUS
-#define BWD_CUS 1
-#endif
-static int bwd_grid(int rows, int D, int per_cu) {
-    const int block = ((D / 4) + 63) / 64 * 64;
-    int grid = (rows + 3) / 4;
-    const int cap = 256 * (block <= 256 ? 4 : per_cu);
-    return grid > cap ? cap : grid;
+constexpr int BWD_R0 = 2, BWD_CU0 = 4;      // rows per trip and resident workgroups per CU of the LayerNorm-only (mode 0) body
+constexpr int BWD_RS = 3, BWD_CUS = 1;      // ... of the LDS-staged FDDT(diag)+LN body: 3 rows x 1 workgroup measured 126 us, 2 x 2: 137, 4 x 1: 128,
+                                            // 3 x 2: 131, 2 x 1: 129 (one block reduction per trip: 32 us of it)
+constexpr int BWD_RG = 2, BWD_CUG = 2;      // ... of the generic body
+constexpr int BWD_STAGED_LDS_MAX = 150 * 1024;       // the row stages must fit the CU's 160 KiB of LDS
+static_assert(BWD_CU0 >= BWD_CUS && BWD_CU0 >= BWD_CUG, "dicow_fddt_ln_bwd_ws_bytes sizes the workspace for BWD_CU0 workgroups per CU");
+
+// Resident workgroups per CU of a backward column-owner body: the measured count of the body; narrow rows (up to 256 threads) always four.
+static int bwd_per_cu(int D, int measured) { return row_block(D) <= 256 ? 4 : measured; }
+// Partial column-sum rows such a body leaves in the workspace = its capped grid, a workgroup per ROWS_R rows.
+static int bwd_ws_grid(int rows, int per_cu) {
+    const int grid = dicow_cdiv(rows, ROWS_R);
+    return grid > ROW_CUS * per_cu ? ROW_CUS * per_cu : grid;
 }
 
-extern "C" int64_t dicow_fddt_ln_bwd_ws_bytes(int rows, int D) { return (int64_t)bwd_grid(rows, D, BWD_CU0 > BWD_CUS ? BWD_CU0 : BWD_CUS) * 11 * D * 4; }
+extern "C" int64_t dicow_fddt_ln_bwd_ws_bytes(int rows, int D) { return (int64_t)bwd_ws_grid(rows, bwd_per_cu(D, BWD_CU0)) * 11 * D * 4; }
 
-extern "C" int dicow_fddt_ln_bwd(const dicow_fddt_ln_bwd_args* a, void* stream) {
+static rows_plan_t rows_bwd_plan(const dicow_fddt_ln_bwd_args* a) {
+    const int block = row_block(a->D);
+    const bool ln0 = block <= 512 && a->mode == 0 && a->ln_w;
+    // LDS-staged body: the encoder-layer shape (every FDDT vector present, fp32 in, bf16 d_y, residual gradient, no pos)
+    const bool staged = block <= 512 && block * 4 == a->D && a->D % 8 == 0 && a->mode == 1 && a->ln_w && !a->in_bf16 && !a->dy_f32 && a->g_res &&
+                        a->g_out && !a->pos && all_fddt_vectors(a) && (int64_t)a->rows * a->D * 4 < (1ll << 31) &&      // (32-bit buffer offsets)
+                        2 * BWD_RS * 10 * a->D <= BWD_STAGED_LDS_MAX;
+    const int per_cu = bwd_per_cu(a->D, ln0 ? BWD_CU0 : staged ? BWD_CUS : BWD_CUG);
+    rows_plan_t p = {ROWS_BWD_GENERIC, block, dicow_cdiv(a->rows, ROWS_R), 0, per_cu, bwd_ws_grid(a->rows, per_cu)};
+    if (ln0 && !a->in_bf16 && !a->pos && wave_width(a->D) && (a->g_out || a->g_out_bf16)) {
+        p.body = ROWS_BWD_LN_WAVE;
+        p.block = LBW_WAVES * 64;
+        p.grid = dicow_cdiv(a->rows, LBW_WAVES);
+        if (p.grid > p.ws_grid) p.grid = p.ws_grid;              // (the workspace is sized for `ws_grid` partial rows)
+        p.lds = 3 * a->D * 4;
+        p.per_cu = ASK_OCCUPANCY;
+    } else if (block > 512) {
+        p.body = ROWS_BWD_GENERIC_1024;
+    } else if (staged) {
+        p.body = a->g_out_bf16 ? ROWS_BWD_STAGED_BF16 : ROWS_BWD_STAGED_F32;
+        p.lds = 2 * BWD_RS * 10 * a->D;
+    } else if (ln0) {
+        p.body = ROWS_BWD_LN_ONLY;
+    }
+    return p;
+}
+
+static int rows_bwd_validate(const dicow_fddt_ln_bwd_args* a) {
     DICOW_REQUIRE(a && a->h_in && a->rows > 0 && a->D > 0, "fddt_ln_bwd: null/empty input");
     DICOW_REQUIRE(a->D % 4 == 0 && a->D <= 4096, "fddt_ln_bwd: D=%d must be a multiple of 4 and <= 4096", a->D);
     DICOW_REQUIRE(a->mode >= 0 && a->mode <= 2, "fddt_ln_bwd: bad mode %d", a->mode);
     DICOW_REQUIRE(a->mode == 0 || (a->stno && a->T > 0), "fddt_ln_bwd: mode %d needs stno and T", a->mode);
     DICOW_REQUIRE(a->ln_w == nullptr || (a->mean && a->rstd && a->d_y), "fddt_ln_bwd: LayerNorm needs mean/rstd/d_y");
     DICOW_REQUIRE(a->ln_w || a->g_res, "fddt_ln_bwd: no incoming gradient");
-    const int block = pick_block(a->D);
-#ifdef DICOW_ABLATIONS
-    static const int r_env = getenv("DICOW_ROW_R") ? atoi(getenv("DICOW_ROW_R")) : 0;       // diagnostic builds only: 0 = auto, 9 = generic body
-#else
-    constexpr int r_env = 0;
-#endif
-    const bool ln0 = block <= 512 && r_env != 9 && a->mode == 0 && a->ln_w;
-    // LDS-staged body: the encoder-layer shape (every FDDT vector present, fp32 in, bf16 d_y, residual gradient, no pos)
-    const bool staged = block <= 512 && block * 4 == a->D && a->D % 8 == 0 && r_env != 9 && r_env != 8 && a->mode == 1 && a->ln_w && !a->in_bf16 &&
-                        !a->dy_f32 && a->g_res && a->g_out && !a->pos && a->w[0] && a->w[1] && a->w[2] && a->w[3] &&
-                        a->b[0] && a->b[1] && a->b[2] && a->b[3] && (int64_t)a->rows * a->D * 4 < (1ll << 31) &&
-                        (BWD_DEPTH + 1) * BWD_RS * 10 * a->D <= 150 * 1024;       // the row stages must fit the CU's 160 KiB of LDS
-    static const bool attr_set = [] {
-        (void)hipFuncSetAttribute((const void*)fddt_ln_bwd_staged_kernel<BWD_RS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute((const void*)fddt_ln_bwd_staged_kernel<BWD_RS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        return true; }();
-    (void)attr_set;
-    const int grid = bwd_grid(a->rows, a->D, ln0 ? BWD_CU0 : staged ? BWD_CUS : 2);
+    return DICOW_OK;
+}
+
+extern "C" const char* dicow_fddt_ln_bwd_route(const dicow_fddt_ln_bwd_args* a) {
+    return rows_bwd_validate(a) == DICOW_OK ? rows_body_name[rows_bwd_plan(a).body] : nullptr;
+}
+
+extern "C" int dicow_fddt_ln_bwd(const dicow_fddt_ln_bwd_args* a, void* stream) {
+    if (const int rc = rows_bwd_validate(a)) return rc;
+    const rows_plan_t p = rows_bwd_plan(a);
     const int D = a->D;
     float* outs[11] = {a->ln_w ? a->dln_w : nullptr, a->ln_w ? a->dln_b : nullptr, a->colsum_out,
                        a->mode == 1 ? a->dw[0] : nullptr, a->mode == 1 ? a->dw[1] : nullptr, a->mode == 1 ? a->dw[2] : nullptr,
@@ -1224,48 +1091,25 @@ extern "C" int dicow_fddt_ln_bwd(const dicow_fddt_ln_bwd_args* a, void* stream) 
                        a->mode != 0 ? a->db[2] : nullptr, a->mode != 0 ? a->db[3] : nullptr};
     bool any = false;
     for (int k = 0; k < 11; ++k) any = any || outs[k];
-    DICOW_REQUIRE(!any || (a->ws && a->ws_bytes >= (int64_t)grid * 11 * D * 4),
-                  "fddt_ln_bwd: workspace too small (need %ld bytes)", (long)grid * 11 * D * 4);
-    hipStream_t st = (hipStream_t)stream;
-    if (LBW_ON && ln0 && r_env == 0 && !a->in_bf16 && !a->pos && a->D % 256 == 0 && a->D >= 512 && a->D <= 1280 && (a->g_out || a->g_out_bf16)) {
-        const int nc = a->D / 256;
-        const void* fn = nc == 5 ? (const void*)ln_bwd_wave_kernel<5> : nc == 4 ? (const void*)ln_bwd_wave_kernel<4>
-                       : nc == 3 ? (const void*)ln_bwd_wave_kernel<3> : (const void*)ln_bwd_wave_kernel<2>;
-        static int occb[6] = {0};
-        int per_cu = __atomic_load_n(&occb[nc], __ATOMIC_RELAXED);
-        const int lds = 3 * D * 4;
-        if (per_cu == 0) {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, LBW_WAVES * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-            __atomic_store_n(&occb[nc], per_cu, __ATOMIC_RELAXED);
-        }
-        int gw = dicow_cdiv(a->rows, LBW_WAVES);
-        if (gw > 256 * per_cu) gw = 256 * per_cu;
-        if (gw > grid) gw = grid;                                // (the workspace is sized for `grid` partial rows)
-        switch (nc) {
-            case 5: hipLaunchKernelGGL(ln_bwd_wave_kernel<5>, dim3(gw), dim3(LBW_WAVES * 64), lds, st, *a); break;
-            case 4: hipLaunchKernelGGL(ln_bwd_wave_kernel<4>, dim3(gw), dim3(LBW_WAVES * 64), lds, st, *a); break;
-            case 3: hipLaunchKernelGGL(ln_bwd_wave_kernel<3>, dim3(gw), dim3(LBW_WAVES * 64), lds, st, *a); break;
-            default: hipLaunchKernelGGL(ln_bwd_wave_kernel<2>, dim3(gw), dim3(LBW_WAVES * 64), lds, st, *a); break;
-        }
-        DICOW_CHECK_LAUNCH("ln_bwd_wave");
-        if (any) return dicow_launch_reduce_multi(reinterpret_cast<const float*>(a->ws), gw, (int64_t)11 * D, D, outs, 11, D, st);
-        return DICOW_OK;
+    DICOW_REQUIRE(!any || (a->ws && a->ws_bytes >= (int64_t)p.ws_grid * 11 * D * 4),
+                  "fddt_ln_bwd: workspace too small (need %ld bytes)", (long)p.ws_grid * 11 * D * 4);
+    const hipStream_t st = (hipStream_t)stream;
+    static const bool attr_set = [] {
+        (void)hipFuncSetAttribute((const void*)fddt_ln_bwd_staged_kernel<BWD_RS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_STAGED_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)fddt_ln_bwd_staged_kernel<BWD_RS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_STAGED_LDS_MAX);
+        return true; }();
+    (void)attr_set;
+    int parts = 0;                                               // partial rows the body left in the workspace
+    switch (p.body) {
+        case ROWS_BWD_LN_WAVE: parts = LAUNCH_WAVE_ROWS(ln_bwd_wave_kernel, p, *a, st); break;
+        case ROWS_BWD_GENERIC_1024: parts = launch_rows<fddt_ln_bwd_kernel<BWD_RG, 1024>>(p, *a, st); break;
+        case ROWS_BWD_GENERIC: parts = launch_rows<fddt_ln_bwd_kernel<BWD_RG, 512>>(p, *a, st); break;
+        case ROWS_BWD_STAGED_BF16: parts = launch_rows<fddt_ln_bwd_staged_kernel<BWD_RS, true>>(p, *a, st); break;
+        case ROWS_BWD_STAGED_F32: parts = launch_rows<fddt_ln_bwd_staged_kernel<BWD_RS, false>>(p, *a, st); break;
+        default: parts = launch_rows<fddt_ln_bwd_kernel<BWD_R0, 512, 0, 1>>(p, *a, st); break;      // ROWS_BWD_LN_ONLY
     }
-    if (block > 512)
-        hipLaunchKernelGGL((fddt_ln_bwd_kernel<2, 1024>), dim3(grid), dim3(block), 0, st, *a);
-    else if (r_env == 9)                                                                    // generic body (ablation)
-        hipLaunchKernelGGL((fddt_ln_bwd_kernel<2, 512>), dim3(grid), dim3(block), 0, st, *a);
-    else if (staged && a->g_out_bf16)
-        hipLaunchKernelGGL((fddt_ln_bwd_staged_kernel<BWD_RS, true>), dim3(grid), dim3(block), (BWD_DEPTH + 1) * BWD_RS * 10 * a->D, st, *a);
-    else if (staged)
-        hipLaunchKernelGGL((fddt_ln_bwd_staged_kernel<BWD_RS, false>), dim3(grid), dim3(block), (BWD_DEPTH + 1) * BWD_RS * 10 * a->D, st, *a);
-    else if (ln0)
-        hipLaunchKernelGGL((fddt_ln_bwd_kernel<BWD_R0, 512, 0, 1>), dim3(grid), dim3(block), 0, st, *a);
-    else
-        hipLaunchKernelGGL((fddt_ln_bwd_kernel<2, 512>), dim3(grid), dim3(block), 0, st, *a);
-    DICOW_CHECK_LAUNCH("fddt_ln_bwd");
-    if (any) return dicow_launch_reduce_multi(reinterpret_cast<const float*>(a->ws), grid, (int64_t)11 * D, D, outs, 11, D,
-                                              (hipStream_t)stream);
+    ROWS_CHECK_LAUNCH("fddt_ln_bwd", p);
+    if (any) return dicow_launch_reduce_multi(reinterpret_cast<const float*>(a->ws), parts, (int64_t)11 * D, D, outs, 11, D, st);
     return DICOW_OK;
 }
 
