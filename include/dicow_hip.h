@@ -254,6 +254,33 @@ typedef struct {
 } dicow_attn_fwd_args;
 int dicow_attn_fwd(const dicow_attn_fwd_args* a, void* stream);
 
+/* The decoder step's attention (ONE query row per decoder row) with the K/V row chosen per query row: softmax(q K^T) V, head_dim 64,
+ * scaling 1.0 (q pre-scaled), bf16 in and out, fp32 inside, fixed summation order (two launches give the same bits).  Same
+ * arithmetic as dicow_attn_fwd with Lq = 1 (HF:modeling_whisper.py:469-494, the decoder layer's cached self- and cross-attention),
+ * but the key/value of position t of row r need not live in row r's own cache:
+ *   SHARED mode   (anc == NULL): row r reads slot r / group.  The `group` beams of one window share ONE copy of the cross-attention
+ *                 K/V (HF's generate repeats the encoder output num_beams times); it is read from memory once per (slot, head) and
+ *                 used for all `group` rows.  n_slots == R / group; group == 1 is the plain decode step.
+ *   ANCESTRY mode (anc != NULL): key and value t of row r come from slot anc[r * anc_rs + t]; n_slots == R.  This replaces the cache
+ *                 reorder of beam search (the reference's _beam_search, src/models/dicow/generation.py:815-1153, calls
+ *                 _temporary_reorder_cache(past_key_values, beam_idx): an index_select copy of every layer's K and V per token):
+ *                 the caches stay where they were written and the table records, per row and position, which slot wrote it.
+ *                 The kernel CLAMPS every table entry into [0, n_slots) before it forms an address: a wrong table gives wrong
+ *                 numbers, never a read outside the n_slots caches.
+ * q/o: bf16 [R, H, 64], element (r, h, d) at base + r*rs + h*64 + d.  k/v: bf16, element (slot, t, h, d) at
+ * base + slot*bs + t*rs + h*64 + d.  Strides in elements; q/k/v bases 16-byte aligned, q_rs/k_rs/v_rs/k_bs/v_bs multiples of 8.
+ * Any Lk >= 1, any H >= 1, group 1..DICOW_ATTN_DECODE_MAX_GROUP.  DICOW_ERR_INVALID (and no launch) for a group outside that range,
+ * R % group != 0, Lk < 1, n_slots inconsistent with the mode, anc_rs < Lk or a NULL q/k/v/o. */
+#define DICOW_ATTN_DECODE_MAX_GROUP 8
+typedef struct {
+    const void* q; void* o;
+    const void* k; const void* v;
+    int64_t q_rs, o_rs, k_bs, k_rs, v_bs, v_rs;
+    const int32_t* anc; int64_t anc_rs;             /* NULL: shared mode */
+    int R, H, Lk, group, n_slots;
+} dicow_attn_decode_args;
+int dicow_attn_decode(const dicow_attn_decode_args* a, void* stream);
+
 typedef struct {
     const void* q; const void* k; const void* v; const void* o; const void* d_o;
     const float* lse; float* delta;                 /* delta: workspace [2,B,H,Lq] fp32 (-rowsum(dO*O), -lse) */

@@ -1,5 +1,5 @@
 """Time the decoding path at whisper-large-v3-turbo dims: encoder once + KV-cached greedy steps.
-usage: python tools/bench_decode.py [B] [new_tokens]"""
+usage: python tools/bench_decode.py [B] [new_tokens] [g = greedy leg with graph replay] [K = also the beam-search leg]"""
 import sys
 import time
 
@@ -38,13 +38,49 @@ tot_ms = (t2 - t1) * 1e3
 print(f"B={B}: encoder + cross K/V {enc_ms:.1f} ms; generate({N} tokens) {tot_ms:.1f} ms -> {(tot_ms - enc_ms) / (N + 3):.3f} ms per decoder step, "
       f"{B * N / tot_ms * 1e3:.0f} tokens/s, {B / tot_ms * 1e3:.1f} windows/s")
 
-if len(sys.argv) > 4:                                           # beam search, K = argv[4]
-    K = int(sys.argv[4])
-    d2 = GreedyDecoder(model)
-    d2.beam_search(b["input_features"], b["stno_mask"], prompt, 4 + 8, K, eos_token_id=-1)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    seq, sc = d2.beam_search(b["input_features"], b["stno_mask"], prompt, 4 + N, K, eos_token_id=-1)
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) * 1e3
-    print(f"beam search K={K}: B={B}, {seq.shape[1] - 4} tokens in {dt:.1f} ms ({B / dt * 1e3:.1f} windows/s)")
+if len(sys.argv) > 4:                                           # beam search, K = argv[4]: three modes in this one process
+    # reorder          the former path: cross K/V repeated per beam, every cache index_select-copied per token, attn_fwd
+    # indirect         one cross K/V per window + ancestry table (ops.attn_decode), eager launches
+    # indirect+graphs  the same with every position's step replayed from its hipGraph
+    # Each mode gets a warm-up call (graph mode: captures all positions), then REPS interleaved timed calls.
+    import statistics
+    K, REPS = int(sys.argv[4]), 3
+    x, sm, steps = b["input_features"], b["stno_mask"], N + 3
+    modes = [("reorder", GreedyDecoder(model), dict(reorder_caches=True)), ("indirect", GreedyDecoder(model), {}),
+             ("indirect+graphs", GreedyDecoder(model, use_graphs=True), {})]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    enc, tot, ntok = {}, {n: [] for n, _, _ in modes}, {}
+    for name, d, kw in modes:
+        d.beam_search(x, sm, prompt, 4 + N, K, eos_token_id=-1, **kw)
+        enc[name] = timed(lambda: d.encode(x, sm, num_beams=K, **kw))[0]
+    for rep in range(REPS):
+        for name, d, kw in modes:
+            ms, (seq, sc) = timed(lambda: d.beam_search(x, sm, prompt, 4 + N, K, eos_token_id=-1, **kw))
+            tot[name].append(ms)
+            ntok[name] = seq.shape[1] - 4
+    print(f"beam search K={K}, B={B}, {N} tokens ({steps} decoder steps), {REPS} interleaved repetitions per mode")
+    print(f"{'mode':<16} {'encode ms':>9} {'total ms (each repetition)':>30} {'median':>8} {'windows/s':>10} {'ms/step':>8}")
+    for name, _, _ in modes:
+        med = statistics.median(tot[name])
+        reps = " ".join(f"{t:8.1f}" for t in tot[name])
+        print(f"{name:<16} {enc[name]:9.1f} {reps:>30} {med:8.1f} {B / med * 1e3:10.1f} {(med - enc[name]) / steps:8.3f}   ({ntok[name]} tokens)")
+    # where a step's time goes on the indirect path: the decoder step alone (eager launches / graph replay) against the whole loop
+    ids = torch.zeros(B * K, dtype=torch.long, device="cuda")
+    d_e, d_g = modes[1][1], modes[2][1]
+    st_e, st_g = d_e.encode(x, sm, num_beams=K), d_g.encode(x, sm, num_beams=K)
+    # (token id 0 at every position: the step's cost does not depend on the ids; one untimed pass of each first)
+    [d_e._step(ids, t, st_e) for t in range(steps)]
+    [d_g._step_graphed(ids, t, st_g) for t in range(steps)]
+    e_ms = timed(lambda: [d_e._step(ids, t, st_e) for t in range(steps)])[0] / steps
+    g_ms = timed(lambda: [d_g._step_graphed(ids, t, st_g) for t in range(steps)])[0] / steps
+    for name, own in (("indirect", e_ms), ("indirect+graphs", g_ms)):
+        per = (statistics.median(tot[name]) - enc[name]) / steps
+        print(f"{name:<16} decoder step alone {own:.3f} ms; rest of a loop trip (log-softmax over {cfg.vocab_size} columns, two topk, gathers, "
+              f"ancestry update, host syncs) {per - own:.3f} ms")

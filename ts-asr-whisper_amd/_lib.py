@@ -61,6 +61,15 @@ class AttnFwdArgs(C.Structure):
                 ("B", c_i), ("H", c_i), ("Lq", c_i), ("Lk", c_i), ("causal", c_i), ("q_log2", c_i)]
 
 
+class AttnDecodeArgs(C.Structure):
+    _fields_ = [("q", c_vp), ("o", c_vp), ("k", c_vp), ("v", c_vp),
+                ("q_rs", c_i64), ("o_rs", c_i64), ("k_bs", c_i64), ("k_rs", c_i64), ("v_bs", c_i64), ("v_rs", c_i64),
+                ("anc", c_vp), ("anc_rs", c_i64), ("R", c_i), ("H", c_i), ("Lk", c_i), ("group", c_i), ("n_slots", c_i)]
+
+
+ATTN_DECODE_MAX_GROUP = 8
+
+
 class AttnBwdArgs(C.Structure):
     _fields_ = [("q", c_vp), ("k", c_vp), ("v", c_vp), ("o", c_vp), ("d_o", c_vp), ("lse", c_vp), ("delta", c_vp),
                 ("dq", c_vp), ("dk", c_vp), ("dv", c_vp),
@@ -130,6 +139,7 @@ _SIGS = {
     "dicow_gemm_tn": [C.POINTER(GemmTnArgs), c_vp],
     "dicow_gemm_tn_group": [C.POINTER(GemmTnGroupArgs), c_vp],
     "dicow_attn_fwd": [C.POINTER(AttnFwdArgs), c_vp],
+    "dicow_attn_decode": [C.POINTER(AttnDecodeArgs), c_vp],
     "dicow_attn_bwd": [C.POINTER(AttnBwdArgs), c_vp],
     "dicow_attn_bwd_fused_status": [c_vp],
     "dicow_ce_loss_fwd": [C.POINTER(CeArgs), c_vp],

@@ -55,17 +55,36 @@ def timestamp_rules(input_ids, scores, begin_index, eos_token_id, no_timestamps_
     return scores
 
 
+def advance_ancestry(anc, beam_idx, pos):
+    """Ancestry table of a beam search whose self-attention caches are never reordered.  anc int32 [rows, Lmax]: anc[r, t] is the
+    cache slot that holds key / value t of the hypothesis now living in row r (initially anc[r, :] = r).  After the step that
+    wrote position ``pos`` -- every row into its OWN slot -- row r continues the hypothesis of row beam_idx[r] (flat parent rows):
+        anc[r, :pos] <- anc[beam_idx[r], :pos]      the parent's history
+        anc[r, pos]  <- beam_idx[r]                 the parent wrote ``pos`` into its own slot
+    In place on the persistent buffer (the captured decoder step reads it); works on CPU tensors too.  Returns anc."""
+    idx = beam_idx.to(device=anc.device, dtype=torch.long)
+    if pos > 0:
+        anc[:, :pos] = anc[:, :pos].index_select(0, idx)             # (index_select copies before the write)
+    anc[:, pos] = idx.to(anc.dtype)
+    return anc
+
+
+def _rows3(t, B, H):
+    """[B, >=H*64] column slice -> [B, H, 64] strided view."""
+    return t.as_strided((B, H, 64), (t.stride(0), 64, 1), t.storage_offset())
+
+
 class GreedyDecoder:
     """``GreedyDecoder(model).generate(...)`` for a ``DiCoWForConditionalGeneration`` on the GPU."""
 
     def __init__(self, model, use_graphs=False):
         """use_graphs: capture each decoder position's step (~55 launches) into a hipGraph the first time it runs and replay
         it afterwards (the step is launch-bound at B = 16: 0.70 -> 0.30 ms); the KV caches and the token buffer are
-        persistent per batch size so that the captured pointers stay valid across windows.  Weights must not be re-allocated
-        between calls (evaluation)."""
+        persistent per batch size (beam search: per rows and beams) so that the captured pointers stay valid across windows.  Weights must not be re-allocated
+        between calls (evaluation).  Beam search is captured too: its caches are never reordered (see ``beam_search``)."""
         self.model, self.cfg = model, model.config
         self.use_graphs = use_graphs
-        self._persist = {}                       # batch size -> decoding state with static buffers and captured graphs
+        self._persist = {}                       # rows (beam states: (rows, beams)) -> decoding state with static buffers and captured graphs
 
     def _step_graphed(self, ids, t, st):
         st.ids_in.copy_(ids)
@@ -101,11 +120,19 @@ class GreedyDecoder:
             qkv = linear_fwd(ln(h, lyr.self_attn_layer_norm), w.sa.qkv, B, flags=L.EPI_SCALE_N, scale=0.125, scale_ncols=D)
             c.k[:, t].copy_(qkv[:, D:2 * D])
             c.v[:, t].copy_(qkv[:, 2 * D:])
-            ops.attn_fwd(heads(qkv[:, :D], B, 1, H), c.k[:, :t + 1].view(B, t + 1, H, 64), c.v[:, :t + 1].view(B, t + 1, H, 64),
-                         heads(o, B, 1, H))
+            ck, cv = c.k[:, :t + 1].view(B, t + 1, H, 64), c.v[:, :t + 1].view(B, t + 1, H, 64)
+            if st.group == 1:
+                ops.attn_fwd(heads(qkv[:, :D], B, 1, H), ck, cv, heads(o, B, 1, H))
+            else:                                # beam rows: position j of row r lives in slot anc[r, j] (this step's own: anc[r, t] = r)
+                ops.attn_decode(_rows3(qkv[:, :D], B, H), ck, cv, _rows3(o, B, H), anc=st.anc)
             h = linear_fwd(o, w.sa.o, B, out_dtype=F32, residual=h)
             q = linear_fwd(ln(h, lyr.encoder_attn_layer_norm), w.ca.q, B, flags=L.EPI_SCALE_N, scale=0.125, scale_ncols=D)
-            ops.attn_fwd(heads(q, B, 1, H), heads(c.ckv[:, :D], B, st.T, H), heads(c.ckv[:, D:], B, st.T, H), heads(o, B, 1, H))
+            if st.group == 1:
+                ops.attn_fwd(heads(q, B, 1, H), heads(c.ckv[:, :D], B, st.T, H), heads(c.ckv[:, D:], B, st.T, H), heads(o, B, 1, H))
+            else:                                # the beams of a window share its cross-attention K/V
+                B0 = B // st.group
+                ops.attn_decode(_rows3(q, B, H), heads(c.ckv[:, :D], B0, st.T, H), heads(c.ckv[:, D:], B0, st.T, H), _rows3(o, B, H),
+                                group=st.group)
             h = linear_fwd(o, w.ca.o, B, out_dtype=F32, residual=h)
             a = linear_fwd(ln(h, lyr.final_layer_norm), w.fc1, B, flags=L.EPI_GELU)
             h = linear_fwd(a, w.fc2, B, out_dtype=F32, residual=h)
@@ -114,10 +141,12 @@ class GreedyDecoder:
         return logits[:, :cfg.vocab_size]
 
     @torch.no_grad()
-    def encode(self, input_features, stno_mask, enrollments=None, num_beams=1):
+    def encode(self, input_features, stno_mask, enrollments=None, num_beams=1, reorder_caches=False):
         """Encoder once + the cross-attention K/V of every decoder layer once.  Returns the decoding state.
-        num_beams > 1: the decoding state has batch x num_beams rows (the encoder and the K/V projections still run once per
-        window; their result is repeated per beam)."""
+        num_beams > 1: the decoding state has batch x num_beams rows.  The cross-attention K/V stay [batch * T, 2D] -- one copy
+        per window, read by its beams through ops.attn_decode(group=num_beams) -- and the self-attention caches are addressed
+        through the ancestry table ``st.anc`` (``st.group = num_beams``).  reorder_caches=True: the layout of a greedy state
+        with batch x num_beams rows instead (``st.group = 1``): the K/V repeated per beam, caches reordered by the caller."""
         model, cfg = self.model, self.cfg
         if not input_features.is_cuda:
             raise L.DicowError("GreedyDecoder: tensors must be on the GPU (no CPU fallback)")
@@ -128,20 +157,26 @@ class GreedyDecoder:
         enc_bf = ops.cast_bf16(enc_out.contiguous().to(F32)).view(B0 * T, D)
         Lmax = cfg.max_target_positions
         dev = enc_out.device
-        st = self._persist.get(B) if self.use_graphs else None
+        group = 1 if reorder_caches else num_beams
+        Bc = B0 if group > 1 else B                                  # rows of cross-attention K/V
+        key = B if group == 1 else (B, group)                        # a beam state never collides with a greedy state of as many rows
+        st = self._persist.get(key) if self.use_graphs else None
         if st is None or st.W is not W or st.T != T:
-            st = NS(B=B, T=T, W=W, layers=[], graphs={}, warm=False, pool=None, ids_in=torch.zeros(B, dtype=torch.long, device=dev))
+            st = NS(B=B, T=T, W=W, group=group, anc=None, layers=[], graphs={}, warm=False, pool=None,
+                    ids_in=torch.zeros(B, dtype=torch.long, device=dev))
+            if group > 1:
+                st.anc = torch.arange(B, dtype=torch.int32, device=dev)[:, None].repeat(1, Lmax)
             for w in W.layers:
-                st.layers.append(NS(ckv=torch.empty(B * T, w.ca.kv.N, dtype=BF16, device=dev),
+                st.layers.append(NS(ckv=torch.empty(Bc * T, w.ca.kv.N, dtype=BF16, device=dev),
                                     k=torch.empty(B, Lmax, D, dtype=BF16, device=dev),
                                     v=torch.empty(B, Lmax, D, dtype=BF16, device=dev)))
             if self.use_graphs:
                 st.pool = torch.cuda.graph_pool_handle()
-                self._persist[B] = st
+                self._persist[key] = st
         st.enc_out = enc_out
         for w, c in zip(W.layers, st.layers):
-            if num_beams == 1:
-                linear_fwd(enc_bf, w.ca.kv, B * T, out=c.ckv)
+            if Bc == B0:
+                linear_fwd(enc_bf, w.ca.kv, B0 * T, out=c.ckv)
             else:
                 kv = linear_fwd(enc_bf, w.ca.kv, B0 * T)
                 c.ckv.view(B0, num_beams, T, -1).copy_(kv.view(B0, 1, T, -1).expand(B0, num_beams, T, kv.shape[1]))
@@ -168,18 +203,31 @@ class GreedyDecoder:
     @torch.no_grad()
     def beam_search(self, input_features, stno_mask, decoder_input_ids, max_length, num_beams, eos_token_id=None, pad_token_id=None,
                     length_penalty=1.0, early_stopping=False, suppress_tokens=None, begin_suppress_tokens=None, enrollments=None,
-                    timestamps=None, ctc=None):
+                    timestamps=None, ctc=None, reorder_caches=False):
         """Beam search as the reference runs it (DiCoWGenerationMixin._beam_search, generation.py:815-1153, on transformers'
         vectorised beam helpers): per step the top 2K continuations over beams x vocabulary, the K best unfinished keep running,
         finished ones compete for the K result slots with length-penalised scores; processors act on log-probabilities
         (suppress lists, timestamp rules, joint CTC term without a second log-softmax, generation.py:249-268); KV caches and
-        the CTC states follow ``beam_idx``.  Returns (sequences [B, <= max_length], scores [B]) of the best hypothesis."""
+        the CTC states follow ``beam_idx``.  Returns (sequences [B, <= max_length], scores [B]) of the best hypothesis.
+
+        The caches follow their beams WITHOUT being copied: a window's cross-attention K/V exist once and are read by its K
+        rows (ops.attn_decode, group=K); every row writes its self-attention key / value into its own slot and reads position j
+        from slot ``st.anc[r, j]``, which ``advance_ancestry`` updates per token (one [B K, Lmax] int32 gather instead of
+        2 x layers cache copies).  The step itself therefore touches fixed buffers only and is captured / replayed like the
+        greedy one under ``use_graphs``; the top-2K selection, the processors and the ancestry update stay outside the graph.
+        reorder_caches=True: the former path (K/V repeated per beam, index_select copies of every cache per token, attn_fwd) --
+        the A/B partner of the tests and tools/bench_decode.py, and what K > ops' MAX_GROUP falls back to; it cannot be graphed."""
         cfg, K = self.cfg, int(num_beams)
         eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
         pad = cfg.pad_token_id if pad_token_id is None else pad_token_id
-        if self.use_graphs:
-            raise L.DicowError("beam_search reorders the KV caches every step: use a decoder without graph capture")
-        st = self.encode(input_features, stno_mask, enrollments, num_beams=K)
+        reorder_caches = bool(reorder_caches) or K > L.ATTN_DECODE_MAX_GROUP
+        if self.use_graphs and (reorder_caches or K == 1):           # (one beam: no indirect state; refused under graphs as before)
+            raise L.DicowError("beam_search(reorder_caches=True) (also: more than %d beams) copies the KV caches every step: use a "
+                               "decoder without graph capture" % L.ATTN_DECODE_MAX_GROUP)
+        st = self.encode(input_features, stno_mask, enrollments, num_beams=K, reorder_caches=reorder_caches)
+        if st.anc is not None:
+            st.anc.copy_(torch.arange(st.B, dtype=torch.int32, device=st.anc.device)[:, None].expand_as(st.anc))
+        step = self._step_graphed if self.use_graphs else self._step
         dev = st.enc_out.device
         prompt = decoder_input_ids.to(dev)
         B, P = prompt.shape
@@ -214,11 +262,11 @@ class GreedyDecoder:
             return torch.take_along_dim(t, idx, dim=1)
 
         for t in range(P - 1):                                       # prefill: every beam of a row starts from the same prompt
-            self._step(run_seq[:, :, t].reshape(-1), t, st)
+            step(run_seq[:, :, t].reshape(-1), t, st)
         cur = P
         while True:
             flat = run_seq[:, :, :cur].reshape(B * K, cur)
-            logp = torch.log_softmax(self._step(flat[:, -1].contiguous(), cur - 1, st).float(), dim=-1)
+            logp = torch.log_softmax(step(flat[:, -1].contiguous(), cur - 1, st).float(), dim=-1)
             if sup is not None:
                 logp[:, sup] = -float("inf")
             if bsup is not None and cur == P:
@@ -246,9 +294,12 @@ class GreedyDecoder:
             seqs, fin_sc = gather(torch.cat((seqs, tk_seq), dim=1), top), gather(m_sc, top)
             fin_idx, is_fin = gather(torch.cat((fin_idx, tk_idx), dim=1), top), gather(torch.cat((is_fin, just), dim=1), top)
             beam_idx = run_idx[..., cur - P].reshape(-1).long()
-            for c in st.layers:                                      # the caches follow their beams
-                c.k[:, :cur].copy_(c.k[:, :cur].index_select(0, beam_idx))
-                c.v[:, :cur].copy_(c.v[:, :cur].index_select(0, beam_idx))
+            if st.anc is not None:                                   # the caches stay put; the table follows the beams
+                advance_ancestry(st.anc, beam_idx, cur - 1)
+            else:
+                for c in st.layers:                                  # the caches follow their beams
+                    c.k[:, :cur].copy_(c.k[:, :cur].index_select(0, beam_idx))
+                    c.v[:, :cur].copy_(c.v[:, :cur].index_select(0, beam_idx))
             if rescorer is not None:
                 rescorer.update_state(run_seq.reshape(B * K, -1)[:, cur], beam_idx)
             cur += 1
@@ -589,6 +640,9 @@ class LongFormDecoder:
                    pad_token_id=None, max_new_tokens=None, enrollments=None, **gen_kw):
         """input_features [B, M, T_total] (T_total a multiple of nothing in particular), stno_mask [B, 4, T_total / 2],
         max_frames [B] valid feature frames per recording, decoder_input_ids [1 or B, P] the forced prompt.
+        gen_kw: suppress_tokens, begin_suppress_tokens, max_initial_timestamp_index, ctc, the fallback arguments, and for
+        num_beams > 1 length_penalty, early_stopping and reorder_caches (False: beam_search's default beam-indirect caches; True: its
+        former copying path).
         Returns per recording a list of segments dict(start, end, tokens) in seconds / token ids."""
         cfg = self.cfg
         eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
@@ -629,7 +683,8 @@ class LongFormDecoder:
             elif self.num_beams > 1:
                 seqs, _ = self.decoder.beam_search(feats, stno, prompt[active], P + n_new, self.num_beams,
                                                    length_penalty=gen_kw.get("length_penalty", 1.0),
-                                                   early_stopping=gen_kw.get("early_stopping", False), **kw)
+                                                   early_stopping=gen_kw.get("early_stopping", False),
+                                                   reorder_caches=gen_kw.get("reorder_caches", False), **kw)
                 tok_lists = [seqs[i, P:].tolist() for i in range(len(active))]
             else:
                 seqs = self.decoder.generate(feats, stno, prompt[active], n_new, **kw)

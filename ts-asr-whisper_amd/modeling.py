@@ -807,11 +807,16 @@ class DiCoWForConditionalGeneration(_ModelBase):
         if not hasattr(self, "_decoder"):
             self._decoder = GreedyDecoder(self)
         if beams > 1:                                        # reference: generation_num_beams 5 in configs/decode/*_beam_joint.yaml
-            seq, _ = self._decoder.beam_search(input_features, stno_mask, decoder_input_ids, P + max_new_tokens, beams,
-                                               eos_token_id=get("eos_token_id", cfg.eos_token_id), pad_token_id=get("pad_token_id", cfg.pad_token_id),
-                                               length_penalty=get("length_penalty", 1.0), early_stopping=get("early_stopping", False),
-                                               suppress_tokens=get("suppress_tokens"), begin_suppress_tokens=get("begin_suppress_tokens"),
-                                               enrollments=enrollments, timestamps=timestamps, ctc=ctc)
+            dec = self._decoder
+            if use_graphs:                                   # (beam search on the beam-indirect caches: its step is captured too)
+                if not hasattr(self, "_decoder_graphed"):
+                    self._decoder_graphed = GreedyDecoder(self, use_graphs=True)
+                dec = self._decoder_graphed
+            seq, _ = dec.beam_search(input_features, stno_mask, decoder_input_ids, P + max_new_tokens, beams,
+                                     eos_token_id=get("eos_token_id", cfg.eos_token_id), pad_token_id=get("pad_token_id", cfg.pad_token_id),
+                                     length_penalty=get("length_penalty", 1.0), early_stopping=get("early_stopping", False),
+                                     suppress_tokens=get("suppress_tokens"), begin_suppress_tokens=get("begin_suppress_tokens"),
+                                     enrollments=enrollments, timestamps=timestamps, ctc=ctc)
             return seq
         dec = self._decoder
         if use_graphs:                                       # hipGraph replay of each decoder position (evaluation: fixed weights)

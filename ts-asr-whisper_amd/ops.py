@@ -399,6 +399,30 @@ def attn_fwd(q, k, v, o, lse=None, causal=False, q_log2=False):
     L.call_struct("dicow_attn_fwd", a)
 
 
+def attn_decode(q, k, v, o, *, group=1, anc=None):
+    """The decoder step's attention with the K/V row chosen per query row (dicow_attn_decode).  q / o [R,H,64] bf16 views,
+    k / v [n_slots,Lk,H,64] bf16 views.  anc None: row r reads slot r // group (n_slots == R // group; the beams of a window share
+    one K/V).  anc int32 [R, >= Lk]: key / value t of row r come from slot anc[r, t] (n_slots == R)."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
+        _req(t, BF16, "attn_decode." + n)
+    for t, n in ((q, "q"), (o, "o")):
+        assert t.dim() == 3 and t.shape[2] == 64 and t.stride(2) == 1 and t.stride(1) == 64, f"attn_decode.{n}: need [R,H,64] view"
+    assert o.shape == q.shape and k.shape == v.shape and k.shape[2] == q.shape[1], "attn_decode: shapes disagree"
+    a = L.AttnDecodeArgs()
+    a.q, a.o, a.k, a.v = q.data_ptr(), o.data_ptr(), k.data_ptr(), v.data_ptr()
+    a.q_rs, a.o_rs = q.stride(0), o.stride(0)
+    a.k_bs, a.k_rs = _bs_rs(k, "k")
+    a.v_bs, a.v_rs = _bs_rs(v, "v")
+    a.R, a.H, a.Lk, a.group, a.n_slots = q.shape[0], q.shape[1], k.shape[1], int(group), k.shape[0]
+    if anc is not None:
+        _req(anc, torch.int32, "attn_decode.anc")
+        assert anc.dim() == 2 and anc.shape[0] == q.shape[0] and anc.stride(1) == 1, "attn_decode.anc: need int32 [R, >= Lk] rows"
+        if anc.shape[1] < a.Lk:
+            raise L.DicowError(f"attn_decode.anc: the table holds {anc.shape[1]} positions per row, fewer than Lk = {a.Lk}")
+        a.anc, a.anc_rs = anc.data_ptr(), anc.stride(0)
+    L.call_struct("dicow_attn_decode", a)
+
+
 _FWS = {}
 ATTN_BWD_FUSED = os.environ.get("DICOW_ATTN_BWD_FUSED", "1") != "0"      # A/B switch of the fused (5-pass) attention backward
 
