@@ -523,3 +523,72 @@ def test_logmel_folded_tables_equal_the_plain_dft():
     w = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(F.N_FFT) / F.N_FFT)
     ref = np.fft.rfft(x[:, :F.N_FFT] * w, axis=1)
     assert np.abs(re_p[:, :201] - ref.real).max() < 2e-6 * scale and np.abs(im_p[:, :201] - ref.imag).max() < 2e-6 * scale
+
+
+# ------------------------------------------------------------------------------------------------ layout-edge helpers (tests/util.py)
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_guarded_checker_flags_every_kind_of_stray_write(dtype):
+    """tests/util.guarded on the CPU: the logical view has the asked stride and starts as NaN in its own dtype; a write inside it
+    passes; a write one row past the end, in the ld gap or in the leading guard is reported with its (row, col)."""
+    from tests.util import guarded
+    rows, cols, ld = 5, 12, 16
+    new = lambda **kw: guarded((rows, cols), ld, dtype, "cpu", **kw)
+    g = new()
+    assert g.view.shape == (rows, cols) and g.view.stride() == (ld, 1) and g.view.data_ptr() % 16 == 0
+    assert bool(g.view.isnan().all()) and g.untouched_inside() == rows * cols
+    assert (g.buf.numel() - g.lead) // ld >= rows + 256
+    g.view.copy_(torch.arange(rows * cols).view(rows, cols))                  # a clean write: every logical element, nothing else
+    g.check()
+    assert g.first_violation() is None and g.untouched_inside() == 0
+    g = new(); g.buf[g.lead + rows * ld + 3] = 1.0                            # one row past the end
+    assert g.first_violation() == (rows, 3)
+    with pytest.raises(AssertionError, match=r"row 5, col 3"):
+        g.check()
+    g = new(); g.buf[g.lead + 2 * ld + cols] = 0.0                            # the first element of row 2's gap (a zero is a write too)
+    assert g.first_violation() == (2, cols)
+    g = new(); g.buf[g.lead - 1] = 1.0                                        # the last element of the leading guard
+    assert g.first_violation() == (-1, ld - 1)
+    g = new(); g.buf[-1] = 1.0                                                # the very last element of the trailing guard
+    assert g.first_violation() == ((g.buf.numel() - g.lead - 1) // ld, ld - 1)
+    g = new(); g.buf[g.lead + 2 * ld + cols] = float("nan")                   # another NaN than the sentinel's bits is still a write
+    assert g.first_violation() == (2, cols)
+    # accumulating outputs: the logical region starts from data, only the outside is sentinel
+    init = torch.full((rows, cols), 0.5)
+    g = new(init=init)
+    assert torch.equal(g.view.float(), init) and g.untouched_inside() == 0
+    g.view.add_(1.0)
+    g.check()
+
+
+def test_guarded_strided_view_and_poisoned_inputs():
+    """A [B, L, 8] slice of packed [B, Lmax, 24] rows: the other columns, the rows L..Lmax of every batch and the tail are guard;
+    tests/util.poisoned keeps the logical values and fills all of that with the chosen poison."""
+    from tests.util import guarded, poisoned, POISON_BIG, SENTINEL16
+    B, Lr, Lmax, ld = 2, 3, 5, 24
+    g = guarded((B, Lr, 8), ld, torch.float32, "cpu", strides=(Lmax * ld, ld, 1), offset=8, span_rows=B * Lmax)
+    g.view.zero_()
+    g.check()
+    g.buf[g.lead + Lr * ld + 8] = 0.0                                         # batch 0, row L (past its end), inside the column slice
+    assert g.first_violation() == (Lr, 8)
+    g = guarded((B, Lr, 8), ld, torch.float32, "cpu", strides=(Lmax * ld, ld, 1), offset=8, span_rows=B * Lmax)
+    g.buf[g.lead + Lmax * ld + 7] = 0.0                                       # batch 1, row 0, the column left of the slice
+    assert g.first_violation() == (Lmax, 7)
+    t = torch.arange(B * Lr * 8, dtype=torch.float32).view(B, Lr, 8)
+    for kind in ("nan", "big", "zero"):
+        v = poisoned(t, ld, "cpu", strides=(Lmax * ld, ld, 1), offset=8, span_rows=B * Lmax, kind=kind)
+        assert torch.equal(v, t) and v.stride() == (Lmax * ld, ld, 1)
+        whole = v.as_strided((B * Lmax + 512, ld), (ld, 1), v.storage_offset() - 8)
+        out = torch.ones(B * Lmax + 512, ld, dtype=torch.bool)
+        for b in range(B):
+            out[b * Lmax:b * Lmax + Lr, 8:16] = False
+        rest = whole[out]
+        if kind == "nan":
+            assert bool((rest.view(torch.int16) == SENTINEL16).all())
+        elif kind == "big":
+            assert bool((rest.abs() == POISON_BIG).all())
+        else:
+            assert bool((rest == 0).all())
+    row = torch.arange(ld, dtype=torch.float32) + 100
+    v = poisoned(t, ld, "cpu", strides=(Lmax * ld, ld, 1), offset=8, span_rows=B * Lmax, poison_row=row)
+    whole = v.as_strided((B * Lmax + 512, ld), (ld, 1), v.storage_offset() - 8)
+    assert torch.equal(v, t) and torch.equal(whole[Lr], row) and torch.equal(whole[-1], row) and torch.equal(whole[0, :8], row[:8])

@@ -183,3 +183,119 @@ def f20_batches(case, K, ts0=None):
             b["enrollments"] = {"input_features": mel[(2 + j) * B:(3 + j) * B], "stno_mask": hashed_stno(B, T, f"f20.{case}.{j}.enr.stno")}
         two.append(b)
     return [two[k % 2] for k in range(K)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Layout-edge helpers (tests/test_gpu_layout_edges.py): outputs inside guard bands, inputs inside poison.  Plain torch, any device.
+SENTINEL16 = 0x7FC1          # every 16-bit word of a guard: bf16 0x7FC1 and fp32 0x7FC17FC1 are both quiet NaNs, so a stray
+                             # read-modify-write shows as well as a stray store
+GUARD_ROWS = 256             # trailing guard rows: taller than any output tile of the library (256 x 256 is the largest)
+POISON_BIG = 3.0e4           # the finite poison (bf16-exact neighbourhood of 2^15): one such operand swamps a product of O(1) terms
+
+
+def _flat_index_mask(total, shape, strides, offset):
+    m = torch.zeros(total, dtype=torch.bool)
+    m.as_strided(tuple(shape), tuple(strides), offset).fill_(True)
+    return m
+
+
+class Guarded:
+    """One flat buffer [lead guard | span rows of `ld` elements | >= GUARD_ROWS guard rows]; `view` is the logical region (a strided
+    view into the span, stride(-2) == ld for the plain 2-D case), everything else holds the sentinel.  check() compares the whole
+    buffer outside the logical region with the sentinel through an integer view and names the first offending (row, col) -- row
+    and col counted in the span's [*, ld] grid, so the leading guard has negative rows and the `ld - cols` gap has col >= cols."""
+
+    def __init__(self, buf, view, lead, ld, inside, name):
+        self.buf, self.view, self.lead, self.ld, self.inside, self.name = buf, view, lead, ld, inside, name
+
+    def outside_words(self):
+        """The 16-bit words of every element outside the logical region, [n_outside, itemsize / 2] (int16)."""
+        w = self.buf.view(torch.int16).view(self.buf.numel(), -1)
+        return w[~self.inside.to(w.device)]
+
+    def violations(self):
+        """Flat element indices (ascending) outside the logical region whose bits are not the sentinel."""
+        w = self.buf.view(torch.int16).view(self.buf.numel(), -1)
+        bad = (w != SENTINEL16).any(1).cpu() & ~self.inside
+        return torch.nonzero(bad).flatten()
+
+    def first_violation(self):
+        """None, or the (row, col) of the first element outside the logical region that was written."""
+        v = self.violations()
+        if v.numel() == 0:
+            return None
+        i = int(v[0]) - self.lead
+        return (i // self.ld, i % self.ld)          # (floor division: the leading guard gives row < 0)
+
+    def check(self):
+        rc = self.first_violation()
+        assert rc is None, f"{self.name}: element outside the logical region overwritten, first at (row {rc[0]}, col {rc[1]}) of the [*, {self.ld}] grid"
+
+    def untouched_inside(self):
+        """Number of logical elements that still hold the sentinel (accumulate = 0 outputs must leave none)."""
+        w = self.view.contiguous().view(torch.int16).view(self.view.numel(), -1)
+        return int((w == SENTINEL16).all(1).sum())
+
+
+def _layout(shape, ld, strides, offset):
+    shape = tuple(int(s) for s in shape)
+    if strides is None:
+        assert len(shape) <= 2, "give strides for views of more than two dimensions"
+        strides = (ld, 1) if len(shape) == 2 else (1,)
+    last = offset + sum((n - 1) * s for n, s in zip(shape, strides))
+    return shape, tuple(strides), last // ld + 1
+
+
+def guarded(shape, ld, dtype, device="cuda", *, strides=None, offset=0, span_rows=None, init=None, lead_rows=4,
+            trail_rows=GUARD_ROWS, name="out"):
+    """An OUTPUT of logical `shape` inside guard bands.  Plain 2-D: rows x cols with row stride ld >= cols.  Any other view: give
+    `strides` (elements) and `offset` (elements from the start of the span) -- e.g. the [B, L, H, 64] slice of packed [B, Lmax, 3D]
+    rows.  span_rows: rows of ld elements the span holds (default: up to the last logical element's row).  init: values of the
+    logical region for outputs that accumulate (None: the sentinel there too, so an output that must be overwritten can be checked
+    with untouched_inside()).  The base of the view is 256-byte aligned when offset == 0 (the lead guard is a multiple of 64
+    elements on top of torch's allocation alignment); dtype must have 2- or 4-byte elements."""
+    assert torch.empty(0, dtype=dtype).element_size() in (2, 4)
+    shape, strides, need = _layout(shape, ld, strides, offset)
+    span_rows = need if span_rows is None else span_rows
+    assert span_rows >= need and trail_rows >= GUARD_ROWS
+    lead = -(-lead_rows * ld // 64) * 64
+    total = lead + (span_rows + trail_rows) * ld
+    buf = torch.empty(total, dtype=dtype, device=device)
+    buf.view(torch.int16).fill_(SENTINEL16)
+    view = buf.as_strided(shape, strides, lead + offset)
+    if init is not None:
+        view.copy_(init.to(device=device, dtype=dtype))
+    return Guarded(buf, view, lead, ld, _flat_index_mask(total, shape, strides, lead + offset), name)
+
+
+def poisoned(t, ld, device="cuda", *, strides=None, offset=0, span_rows=None, kind="nan", poison_row=None, lead_rows=4,
+             trail_rows=2 * GUARD_ROWS):
+    """An INPUT: the values of `t` in a strided view (layout arguments as in `guarded`) of one allocation in which every other
+    element -- the lead, the row gaps, the rows after the last logical row, the gaps between batches, the tail -- holds poison.
+    kind "nan": the NaN bit pattern of the guards; "big": +-POISON_BIG alternating by element; "zero": zeros (the run the
+    poisoned ones must equal bit for bit).  poison_row ([ld] values): tile this row pattern over the whole allocation instead
+    (attention: keys aligned with the queries, values +100).  The tail is 512 rows: the widest operand tile (the 320 weight rows
+    of a 192 x 320 GEMM tile) stays inside the allocation even if a kernel reads it whole.  Returns the view."""
+    shape, strides, need = _layout(t.shape, ld, strides, offset)
+    span_rows = need if span_rows is None else span_rows
+    lead = -(-lead_rows * ld // 64) * 64
+    rows_total = lead // ld + 1 + span_rows + trail_rows
+    total = lead + (span_rows + trail_rows) * ld
+    if poison_row is not None:
+        assert poison_row.numel() == ld
+        # (row pattern in phase with the span: the lead is filled from its end backwards)
+        flat = poison_row.to(t.dtype).repeat(rows_total + 1)
+        ph = (ld - lead % ld) % ld
+        buf = flat[ph:ph + total].clone().to(device)
+    elif kind == "nan":
+        buf = torch.empty(total, dtype=t.dtype, device=device)
+        buf.view(torch.int16).fill_(SENTINEL16)
+    elif kind == "big":
+        buf = torch.full((total,), POISON_BIG, dtype=t.dtype, device=device)
+        buf[1::2] = -POISON_BIG
+    else:
+        assert kind == "zero", kind
+        buf = torch.zeros(total, dtype=t.dtype, device=device)
+    view = buf.as_strided(shape, strides, lead + offset)
+    view.copy_(t.to(device))
+    return view
