@@ -281,6 +281,62 @@ typedef struct {
 } dicow_attn_decode_args;
 int dicow_attn_decode(const dicow_attn_decode_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ LoRA adapters (decoder)
+ * The low-rank side of y = W x + b + s B (A x), s = alpha / r (reference src/models/containers.py:69-78: peft LoRA of rank 16 on
+ * the decoder's q/k/v/out projections and fc1/fc2).  Three skinny kernels beside the base GEMMs, bf16 operands, fp32 accumulation
+ * on v_mfma_f32_16x16x32_bf16; each reads its large operand once.  Adapters that share an input (or whose outputs are the column
+ * segments of one fused matrix) are handled by ONE launch:
+ *   DENSE mode: one contraction, all R = nseg * r stacked rows at once.
+ *   BLOCK mode (DICOW_LORA_BLOCK): the wide matrix is nseg = R / r column segments of `K` / `N` columns each, segment j works
+ *              with rows [j r, (j + 1) r) of the stacked small operand only.
+ * r in {8, 16, 32, 64}, R % r == 0, R <= DICOW_LORA_MAX_R.  Leading dimensions in elements.  DICOW_ERR_INVALID (and no launch) for
+ * anything else.  Nothing outside [M, columns] of an output is written.
+ * Rounding points: t = bf16(x A^T); the low-rank product is rounded to bf16, multiplied by s, rounded to bf16 and added to the
+ * base result in fp32; the sum is rounded once to the output type (peft's Linear.forward under bf16 autocast). */
+#define DICOW_LORA_MAX_R 192
+#define DICOW_LORA_MAX_SEG 24
+#define DICOW_LORA_BLOCK   1     /* block mode (else dense) */
+#define DICOW_LORA_OUT_F32 2     /* up: P and Y are fp32 (else bf16) */
+#define DICOW_LORA_GELU    4     /* up (bf16 Y): Y = gelu(bf16(sum)), aux (may be NULL) <- gelu'(bf16(sum)): DICOW_EPI_GELU | DICOW_EPI_GELU_DAUX */
+#define DICOW_LORA_MUL_AUX 8     /* up (bf16 Y, FP32 P != Y): Y = bf16((P + v) * aux[m, n]), aux = the saved gelu': DICOW_EPI_MUL_AUX for a dgrad that has an */
+                                 /* adapter's share; P is the base dgrad's fp32 result, so that the product is rounded once, as in the GEMM epilogue      */
+/* T[M, R] = X V^T (bf16).  Dense: X [M, K], V [R, K].  Block: X [M, nseg * K], V [R, K]; T[:, j r + p] = X[:, j K + k] V[j r + p, k]
+ * (the backward's dt_j = dy_j B_j with V = the stacked B_j^T).  K % 32 == 0; X, V 16-byte aligned, ldx / ldv % 8 == 0; T 8-byte
+ * aligned, ldt % 4 == 0. */
+typedef struct {
+    const void* X; const void* V; void* T;
+    int64_t ldx, ldv, ldt;
+    int M, K, R, r, flags;
+} dicow_lora_down_args;
+int dicow_lora_down(const dicow_lora_down_args* a, void* stream);
+/* Y = epi(P + bf16(s_j * bf16(T_j U_j))), P the base GEMM's result (same type and shape as Y; P == Y allowed, ldp then == ldy).
+ * Dense: T [M, R], U [R, N], Y [M, N], s = seg_scale[0] (dx += dt A_stacked; into the fp32 d_enc for the cross-attention k/v).
+ * Block: Y [M, nseg * N], Y[:, j N + n] uses T[:, j r + p] U[j r + p, n] and s_j = seg_scale[j] (the forward's y_j with U = the
+ * stacked B_j^T; the q segment carries the attention scale beside alpha / r).  N % 16 == 0 (block: N % 64 == 0); T, U: ldt % 8
+ * == 0, T 16-byte aligned; P, Y, aux 16-byte aligned with ldp / ldy / ldaux % 8 == 0. */
+typedef struct {
+    const void* T; const void* U; const void* P; void* Y; void* aux;
+    int64_t ldt, ldu, ldp, ldy, ldaux;
+    int M, N, R, r, flags;
+    float seg_scale[DICOW_LORA_MAX_SEG];
+} dicow_lora_up_args;
+int dicow_lora_up(const dicow_lora_up_args* a, void* stream);
+/* G_j (+)= scale * T_j^T P_j, fp32, element (p, n) of segment j at G[j] + p * g_rs + n * g_cs (dA [r, K]: g_rs = K, g_cs = 1;
+ * dB [N, r]: g_rs = 1, g_cs = r); a NULL G[j] is skipped.  Dense: T [M, R], P [M, N]: G[j] = rows [j r, (j + 1) r) of T^T P.
+ * Block: P [M, nseg * N]: G[j] = T[:, j r ..]^T P[:, j N ..].  The contraction over M is cut into row blocks whose partial
+ * results go to `ws` (dicow_lora_wgrad_ws_bytes) and are added in a fixed order by a second launch: no atomics, two runs give
+ * the same bits.  accumulate == 0 overwrites G (its previous contents are not read).  N % 32 == 0; T, P 2-byte elements with any
+ * ld >= the columns used. */
+typedef struct {
+    const void* T; const void* P; float* G[DICOW_LORA_MAX_SEG];
+    int64_t ldt, ldp, g_rs, g_cs;
+    int M, N, R, r, flags;
+    float scale; int accumulate;
+    void* ws; int64_t ws_bytes;
+} dicow_lora_wgrad_args;
+int64_t dicow_lora_wgrad_ws_bytes(int M, int N, int R, int r, int flags);
+int dicow_lora_wgrad(const dicow_lora_wgrad_args* a, void* stream);
+
 typedef struct {
     const void* q; const void* k; const void* v; const void* o; const void* d_o;
     const float* lse; float* delta;                 /* delta: workspace [2,B,H,Lq] fp32 (-rowsum(dO*O), -lse) */

@@ -10,8 +10,8 @@ on a GPU.  The CPU oracle lives in ``oracle/`` and is test infrastructure only.
 from . import _lib  # noqa: F401
 from .config import DiCoWConfig, PRESETS  # noqa: F401
 from .modeling import (FDDT, DiCoWEncoder, DiCoW, DiCoWForConditionalGeneration, SpeakerCommunicationBlock,  # noqa: F401
-                       shift_tokens_right, build_ts_tables)
+                       shift_tokens_right, build_ts_tables, LoRALinear, add_decoder_lora, merge_lora, save_adapter, load_adapter)
 from .optim import DiCoWAdamW, clip_grad_norm_, dicow_optimizer  # noqa: F401
 
 __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalGeneration", "SpeakerCommunicationBlock",
-           "DiCoWAdamW", "clip_grad_norm_", "dicow_optimizer"]
+           "LoRALinear", "add_decoder_lora", "merge_lora", "save_adapter", "load_adapter", "DiCoWAdamW", "clip_grad_norm_", "dicow_optimizer"]

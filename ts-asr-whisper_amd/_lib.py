@@ -69,6 +69,26 @@ class AttnDecodeArgs(C.Structure):
 
 ATTN_DECODE_MAX_GROUP = 8
 
+LORA_MAX_R, LORA_MAX_SEG = 192, 24
+LORA_BLOCK, LORA_OUT_F32, LORA_GELU, LORA_MUL_AUX = 1, 2, 4, 8
+
+
+class LoraDownArgs(C.Structure):
+    _fields_ = [("X", c_vp), ("V", c_vp), ("T", c_vp), ("ldx", c_i64), ("ldv", c_i64), ("ldt", c_i64),
+                ("M", c_i), ("K", c_i), ("R", c_i), ("r", c_i), ("flags", c_i)]
+
+
+class LoraUpArgs(C.Structure):
+    _fields_ = [("T", c_vp), ("U", c_vp), ("P", c_vp), ("Y", c_vp), ("aux", c_vp),
+                ("ldt", c_i64), ("ldu", c_i64), ("ldp", c_i64), ("ldy", c_i64), ("ldaux", c_i64),
+                ("M", c_i), ("N", c_i), ("R", c_i), ("r", c_i), ("flags", c_i), ("seg_scale", c_f * LORA_MAX_SEG)]
+
+
+class LoraWgradArgs(C.Structure):
+    _fields_ = [("T", c_vp), ("P", c_vp), ("G", c_vp * LORA_MAX_SEG), ("ldt", c_i64), ("ldp", c_i64), ("g_rs", c_i64), ("g_cs", c_i64),
+                ("M", c_i), ("N", c_i), ("R", c_i), ("r", c_i), ("flags", c_i), ("scale", c_f), ("accumulate", c_i),
+                ("ws", c_vp), ("ws_bytes", c_i64)]
+
 
 class AttnBwdArgs(C.Structure):
     _fields_ = [("q", c_vp), ("k", c_vp), ("v", c_vp), ("o", c_vp), ("d_o", c_vp), ("lse", c_vp), ("delta", c_vp),
@@ -140,6 +160,9 @@ _SIGS = {
     "dicow_gemm_tn_group": [C.POINTER(GemmTnGroupArgs), c_vp],
     "dicow_attn_fwd": [C.POINTER(AttnFwdArgs), c_vp],
     "dicow_attn_decode": [C.POINTER(AttnDecodeArgs), c_vp],
+    "dicow_lora_down": [C.POINTER(LoraDownArgs), c_vp],
+    "dicow_lora_up": [C.POINTER(LoraUpArgs), c_vp],
+    "dicow_lora_wgrad": [C.POINTER(LoraWgradArgs), c_vp],
     "dicow_attn_bwd": [C.POINTER(AttnBwdArgs), c_vp],
     "dicow_attn_bwd_fused_status": [c_vp],
     "dicow_ce_loss_fwd": [C.POINTER(CeArgs), c_vp],
@@ -235,6 +258,7 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
     "dicow_scb_gate_bwd_ws_bytes": [],
     "dicow_ctc_ws_bytes": [c_i, c_i, c_i],
     "dicow_multi_sumsq_ws_bytes": [c_i64],
+    "dicow_lora_wgrad_ws_bytes": [c_i, c_i, c_i, c_i, c_i],
 }
 
 

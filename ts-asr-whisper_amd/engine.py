@@ -326,6 +326,75 @@ def linear_wgrad(dy, x, gw, M, n_rows=None, group=None, param=None):
     ops.gemm_tn(dy, x, gw, M, N, x.shape[1], lda=dy.stride(0), ldb=x.stride(0), ldc=gw.stride(0), accumulate=acc)
 
 
+# ---- LoRA adapters (reference containers.py:69-78; modeling.LoRALinear).  The adapters of the Linears that share an input -- or whose
+# outputs are the column segments of one fused matrix -- form ONE group: their A matrices stacked [R, K] (one pass over x gives every
+# t_j = bf16(x A_j^T)), their B^T stacked [R, N] (segment j of the output / its gradient works with rows [j r, (j + 1) r) only).
+class LoraW:
+    """bf16 compute copies of one adapter group: A [R, K] and Bt [R, N] (B_j^T stacked), refreshed in place (stable pointers: captured
+    decoding graphs and the saved activations of a running step stay valid)."""
+    __slots__ = ("mods", "r", "s", "R", "K", "N", "A", "Bt")
+
+    def refresh(self):
+        r = self.r
+        for j, m in enumerate(self.mods):
+            ops.cast_transpose_bf16(m.lora_A.weight.detach(), out=self.A[j * r:(j + 1) * r], ld=self.K)
+            ops.cast_transpose_bf16(m.lora_B.weight.detach(), out_t=self.Bt[j * r:(j + 1) * r], ld_t=self.N)
+
+
+def prep_lora(mods, dev):
+    """The adapter group of the (fused) Linear made of `mods`, or None when none of them carries an adapter."""
+    has = [hasattr(m, "lora_A") for m in mods]
+    if not any(has):
+        return None
+    if not all(has) or len({(m.r, m.lora_alpha) for m in mods}) != 1:
+        raise NotImplementedError("LoRA: the projections of one fused Linear (q/k/v, k/v) must all carry adapters of one rank and alpha")
+    la = LoraW()
+    la.mods, la.r, la.s = list(mods), mods[0].r, mods[0].scaling
+    la.R, la.K, la.N = la.r * len(mods), mods[0].in_features, mods[0].out_features
+    la.A, la.Bt = _e((la.R, la.K), BF16, dev), _e((la.R, la.N), BF16, dev)
+    la.refresh()
+    return la
+
+
+def lora_fwd(x, la, y, M, q_scale=None, gelu=False, gelu_aux=None):
+    """The adapters' share of a (fused) Linear, added in place to the base GEMM's result y [M, nseg * N] (bf16, or the fp32 residual
+    stream): y_j = epi(y_j + bf16(s_j bf16(t_j B_j^T))), t = bf16(x A^T).  A no-op (returns None) without adapters; else returns t
+    [M, R] for lora_bwd.  q_scale: the attention scale the base GEMM's EPI_SCALE_N put on segment 0.  gelu: y holds fc1's
+    pre-activation (base GEMM run WITHOUT its GELU epilogue) and leaves as the activation, gelu_aux receives gelu'."""
+    if la is None:
+        return None
+    t = _e((M, la.R), BF16, x.device)
+    ops.lora_down(x, la.A, t, la.r)
+    scales = [la.s] * len(la.mods)
+    if q_scale is not None:
+        scales[0] *= q_scale
+    ops.lora_up(t, la.Bt, y, y, la.r, scales, block=True, gelu=gelu, aux=gelu_aux)
+    return t
+
+
+def lora_bwd(dy, x, t, la, M, G, dx=None, mul_aux=None, dx_out=None):
+    """Backward of lora_fwd: dy [M, nseg * N] bf16 = gradient wrt the (unscaled) Linear output, x the Linear's input, t what lora_fwd
+    returned.  dB_j += s dy_j^T t_j and dA_j += s dt_j^T x go to the sink G (skipped for adapters that do not require grad), and
+    dx (bf16 [M, K] from the base dgrad, or the fp32 d_enc) receives dx += bf16(s bf16(dt A)), dt_j = bf16(dy_j B_j).  mul_aux (the saved
+    gelu' of the layer below): dx is the base dgrad's FP32 result and dx_out = bf16((dx + share) * mul_aux) -- one rounding, as the base
+    GEMM's MUL_AUX epilogue, so that zero adapters change no bit.  No-op without adapters."""
+    if la is None:
+        return
+    r = la.r
+    dt = _e((M, la.R), BF16, dy.device)
+    ops.lora_down(dy, la.Bt, dt, r, block=True)
+    gB = [G.get(m.lora_B.weight) for m in la.mods]
+    gA = [G.get(m.lora_A.weight) for m in la.mods]
+    if any(g is not None for g in gB):
+        ops.lora_wgrad(t, dy, gB, r, la.s, block=True, g_rs=1, g_cs=r,
+                       accumulate=not _first_writer(*[m.lora_B.weight for m, g in zip(la.mods, gB) if g is not None]))
+    if any(g is not None for g in gA):
+        ops.lora_wgrad(dt, x, gA, r, la.s, g_rs=la.K,
+                       accumulate=not _first_writer(*[m.lora_A.weight for m, g in zip(la.mods, gA) if g is not None]))
+    if dx is not None:
+        ops.lora_up(dt, la.A, dx, dx if dx_out is None else dx_out, r, [la.s], mul_aux=mul_aux is not None, aux=mul_aux)
+
+
 def qkv_wgrad(d_qkv, x, gq, gk, gv, M, D, group=None, params=None):
     """Weight gradients of the fused q/k/v projection from ONE TN GEMM (C rows segmented over the three tensors)."""
     if gq is not None and gk is not None and gv is not None and D % 128 == 0:
@@ -1176,11 +1245,24 @@ class DecoderEngine:
             w.ca = prep_attention(lyr.encoder_attn, dev, fuse_qkv=False)
             w.fc1 = prep_linear([lyr.fc1.weight], [lyr.fc1.bias], dev)
             w.fc2 = prep_linear([lyr.fc2.weight], [lyr.fc2.bias], dev)
+            sa, ca = lyr.self_attn, lyr.encoder_attn
+            w.lora = NS(sa_qkv=prep_lora([sa.q_proj, sa.k_proj, sa.v_proj], dev), sa_o=prep_lora([sa.out_proj], dev),
+                        ca_q=prep_lora([ca.q_proj], dev), ca_kv=prep_lora([ca.k_proj, ca.v_proj], dev), ca_o=prep_lora([ca.out_proj], dev),
+                        fc1=prep_lora([lyr.fc1], dev), fc2=prep_lora([lyr.fc2], dev))
             W.layers.append(w)
         W.vpad = _ceil(cfg.vocab_size, 128)
         W.head = prep_linear([self.model.proj_out.weight], None, dev, n_pad=W.vpad)
         self.W = W
         return W
+
+    def refresh_adapters(self):
+        """Only the adapters moved (a LoRA step on a frozen decoder): re-cast their bf16 A / B^T copies in place; the base weights' copies
+        and the LM head stay as they are (same buffers, same contents)."""
+        with ops.cast_group():
+            for w in self.W.layers:
+                for la in vars(w.lora).values():
+                    if la is not None:
+                        la.refresh()
 
     def _layers_fwd(self, enc_bf, B, T, Lq, h):
         """The decoder layers on B sequences: h fp32 [B*Lq, D] (embeddings) -> (last hidden state, per-layer saved activations)."""
@@ -1192,33 +1274,44 @@ class DecoderEngine:
         out = []
         for i, lyr in enumerate(dec.layers):
             w = W.layers[i]
+            la = w.lora
             Ls = NS(h_in=h)
             # causal self-attention
             ln = lyr.self_attn_layer_norm
             Ls.x1, Ls.m1, Ls.r1 = _e((rows, D), BF16, dev), _e((rows,), F32, dev), _e((rows,), F32, dev)
             ops.fddt_ln_fwd(h, rows, D, ln_w=ln.weight.detach(), ln_b=ln.bias.detach(), y_bf16=Ls.x1, mean=Ls.m1, rstd=Ls.r1)
             Ls.qkv = linear_fwd(Ls.x1, w.sa.qkv, rows, flags=L.EPI_SCALE_N, scale=Q_SCALE, scale_ncols=D)
+            Ls.t_qkv = lora_fwd(Ls.x1, la.sa_qkv, Ls.qkv, rows, q_scale=Q_SCALE)
             Ls.o1, Ls.lse1 = _e((rows, D), BF16, dev), _e((B, H, Lq), F32, dev)
             ops.attn_fwd(heads(Ls.qkv[:, :D], B, Lq, H), heads(Ls.qkv[:, D:2 * D], B, Lq, H), heads(Ls.qkv[:, 2 * D:], B, Lq, H),
                          heads(Ls.o1, B, Lq, H), Ls.lse1, causal=True, q_log2=QK_LOG2)
             Ls.h2 = linear_fwd(Ls.o1, w.sa.o, rows, out_dtype=F32, residual=h)
+            Ls.t_o1 = lora_fwd(Ls.o1, la.sa_o, Ls.h2, rows)
             # cross-attention over the encoder output
             ln = lyr.encoder_attn_layer_norm
             Ls.x2, Ls.m2, Ls.r2 = _e((rows, D), BF16, dev), _e((rows,), F32, dev), _e((rows,), F32, dev)
             ops.fddt_ln_fwd(Ls.h2, rows, D, ln_w=ln.weight.detach(), ln_b=ln.bias.detach(), y_bf16=Ls.x2, mean=Ls.m2, rstd=Ls.r2)
             Ls.q = linear_fwd(Ls.x2, w.ca.q, rows, flags=L.EPI_SCALE_N, scale=Q_SCALE, scale_ncols=D)
+            Ls.t_q = lora_fwd(Ls.x2, la.ca_q, Ls.q, rows, q_scale=Q_SCALE)
             Ls.kv = linear_fwd(enc_bf, w.ca.kv, B * T)
+            Ls.t_kv = lora_fwd(enc_bf, la.ca_kv, Ls.kv, B * T)
             Ls.o2, Ls.lse2 = _e((rows, D), BF16, dev), _e((B, H, Lq), F32, dev)
             ops.attn_fwd(heads(Ls.q, B, Lq, H), heads(Ls.kv[:, :D], B, T, H), heads(Ls.kv[:, D:], B, T, H), heads(Ls.o2, B, Lq, H),
                          Ls.lse2, q_log2=QK_LOG2)
             Ls.h3 = linear_fwd(Ls.o2, w.ca.o, rows, out_dtype=F32, residual=Ls.h2)
+            Ls.t_o2 = lora_fwd(Ls.o2, la.ca_o, Ls.h3, rows)
             # feed-forward
             ln = lyr.final_layer_norm
             Ls.x3, Ls.m3, Ls.r3 = _e((rows, D), BF16, dev), _e((rows,), F32, dev), _e((rows,), F32, dev)
             ops.fddt_ln_fwd(Ls.h3, rows, D, ln_w=ln.weight.detach(), ln_b=ln.bias.detach(), y_bf16=Ls.x3, mean=Ls.m3, rstd=Ls.r3)
             Ls.u = _e((rows, F_), BF16, dev)
-            Ls.a = linear_fwd(Ls.x3, w.fc1, rows, gelu_aux=Ls.u)
+            if la.fc1 is None:
+                Ls.a, Ls.t_fc1 = linear_fwd(Ls.x3, w.fc1, rows, gelu_aux=Ls.u), None
+            else:                                # the GELU moves behind the adapter: base GEMM without it, the `up` pass applies it
+                Ls.a = linear_fwd(Ls.x3, w.fc1, rows)
+                Ls.t_fc1 = lora_fwd(Ls.x3, la.fc1, Ls.a, rows, gelu=True, gelu_aux=Ls.u)
             h = linear_fwd(Ls.a, w.fc2, rows, out_dtype=F32, residual=Ls.h3)
+            Ls.t_fc2 = lora_fwd(Ls.a, la.fc2, h, rows)
             out.append(Ls)
         return h, out
 
@@ -1238,7 +1331,9 @@ class DecoderEngine:
         # A FROZEN decoder (the reference's default: frozen keyword "decoder") is row-parallel in both directions -- no parameter gradient
         # is reduced over rows -- so a large even batch runs its decoder layers as two half batches on two streams (SPLIT_FWD above):
         # the decoder's kernels at B x 128 rows fill a third of the chip each, two of them side by side fill two thirds.  The LM head
-        # and the loss stay on the full batch behind the join; everything is bit-identical.
+        # and the loss stay on the full batch behind the join; everything is bit-identical.  TRAINABLE LoRA adapters are decoder parameters:
+        # the condition "no decoder parameter requires grad" below switches the split off by itself for a LoRA step (dA / dB are reduced
+        # over rows); frozen adapters (evaluation) are row-parallel like the base weights and keep it.
         split = (SPLIT_FWD and SPLIT_DEC and B % 2 == 0 and B * T >= SPLIT_FWD_MIN_ROWS and enc_bf.is_cuda
                  and _split_allowed() and not model.proj_out.weight.requires_grad
                  and not any(p.requires_grad for p in dec.parameters()))
@@ -1288,12 +1383,18 @@ class DecoderEngine:
         nl = len(dec.layers)
         for i in range(nl - 1, -1, -1):
             lyr, w, Ls = dec.layers[i], W.layers[i], layers[i]
+            la = w.lora
             # FFN
             linear_wgrad(gb, Ls.a, G.get(lyr.fc2.weight), rows)
-            d_u = linear_dgrad(gb, w.fc2, rows, aux=Ls.u)
+            if la.fc2 is None:
+                d_u = linear_dgrad(gb, w.fc2, rows, aux=Ls.u)
+            else:                                # d_a = gb W2 + the adapter's share first, then gelu' (the `up` pass multiplies: the base GEMM's MUL_AUX would miss the share)
+                d_u = _e((rows, F_), BF16, dev)
+                lora_bwd(gb, Ls.a, Ls.t_fc2, la.fc2, rows, G, dx=linear_dgrad(gb, w.fc2, rows, out_dtype=F32), mul_aux=Ls.u, dx_out=d_u)
             bias_grad(d_u, G.get(lyr.fc1.bias))
             linear_wgrad(d_u, Ls.x3, G.get(lyr.fc1.weight), rows)
             d_x3 = linear_dgrad(d_u, w.fc1, rows)
+            lora_bwd(d_u, Ls.x3, Ls.t_fc1, la.fc1, rows, G, dx=d_x3)
             g3, g3b = _e((rows, D), F32, dev), _e((rows, D), BF16, dev)
             ln = lyr.final_layer_norm
             ops.fddt_ln_bwd(Ls.h3, rows, D, ln_w=ln.weight.detach(), mean=Ls.m3, rstd=Ls.r3, d_y=d_x3, g_res=g, g_out=g3,
@@ -1303,6 +1404,7 @@ class DecoderEngine:
             att = lyr.encoder_attn
             linear_wgrad(g3b, Ls.o2, G.get(att.out_proj.weight), rows)
             d_o2 = linear_dgrad(g3b, w.ca.o, rows)
+            lora_bwd(g3b, Ls.o2, Ls.t_o2, la.ca_o, rows, G, dx=d_o2)
             dq = _e((rows, D), BF16, dev)
             dkv = _e((B * T, 2 * D), BF16, dev)
             delta = _e((2, B, H, Lq), F32, dev)
@@ -1316,7 +1418,9 @@ class DecoderEngine:
             linear_wgrad(dkv[:, D:], enc_bf, G.get(att.v_proj.weight), B * T)
             if d_enc is not None:
                 linear_dgrad(dkv, w.ca.kv, B * T, out=d_enc, accumulate=True)
+            lora_bwd(dkv, enc_bf, Ls.t_kv, la.ca_kv, B * T, G, dx=d_enc)      # (the k/v adapters' share of d_enc: the encoder's gradients need it)
             d_x2 = linear_dgrad(dq, w.ca.q, rows)
+            lora_bwd(dq, Ls.x2, Ls.t_q, la.ca_q, rows, G, dx=d_x2)
             g2, g2b = _e((rows, D), F32, dev), _e((rows, D), BF16, dev)
             ln = lyr.encoder_attn_layer_norm
             ops.fddt_ln_bwd(Ls.h2, rows, D, ln_w=ln.weight.detach(), mean=Ls.m2, rstd=Ls.r2, d_y=d_x2, g_res=g3, g_out=g2,
@@ -1326,6 +1430,7 @@ class DecoderEngine:
             att = lyr.self_attn
             linear_wgrad(g2b, Ls.o1, G.get(att.out_proj.weight), rows)
             d_o1 = linear_dgrad(g2b, w.sa.o, rows)
+            lora_bwd(g2b, Ls.o1, Ls.t_o1, la.sa_o, rows, G, dx=d_o1)
             d_qkv = _e((rows, 3 * D), BF16, dev)
             qkv = Ls.qkv
             ops.attn_bwd(heads(qkv[:, :D], B, Lq, H), heads(qkv[:, D:2 * D], B, Lq, H), heads(qkv[:, 2 * D:], B, Lq, H),
@@ -1337,6 +1442,7 @@ class DecoderEngine:
             linear_wgrad(d_qkv[:, D:2 * D], Ls.x1, G.get(att.k_proj.weight), rows)
             linear_wgrad(d_qkv[:, 2 * D:], Ls.x1, G.get(att.v_proj.weight), rows)
             d_x1 = linear_dgrad(d_qkv, w.sa.qkv, rows)
+            lora_bwd(d_qkv, Ls.x1, Ls.t_qkv, la.sa_qkv, rows, G, dx=d_x1)
             g1, g1b = _e((rows, D), F32, dev), _e((rows, D), BF16, dev)
             ln = lyr.self_attn_layer_norm
             ops.fddt_ln_bwd(Ls.h_in, rows, D, ln_w=ln.weight.detach(), mean=Ls.m1, rstd=Ls.r1, d_y=d_x1, g_res=g2, g_out=g1,

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .engine import heads, linear_fwd
+from .engine import heads, linear_fwd, lora_fwd
 
 F32, BF16 = torch.float32, torch.bfloat16
 
@@ -116,8 +116,9 @@ class GreedyDecoder:
             return x
 
         for i, lyr in enumerate(dec.layers):
-            w, c = W.layers[i], st.layers[i]
+            w, c, la = W.layers[i], st.layers[i], W.layers[i].lora      # (la: the LoRA adapter groups; lora_fwd is a no-op without them)
             qkv = linear_fwd(ln(h, lyr.self_attn_layer_norm), w.sa.qkv, B, flags=L.EPI_SCALE_N, scale=0.125, scale_ncols=D)
+            lora_fwd(x, la.sa_qkv, qkv, B, q_scale=0.125)
             c.k[:, t].copy_(qkv[:, D:2 * D])
             c.v[:, t].copy_(qkv[:, 2 * D:])
             ck, cv = c.k[:, :t + 1].view(B, t + 1, H, 64), c.v[:, :t + 1].view(B, t + 1, H, 64)
@@ -126,7 +127,9 @@ class GreedyDecoder:
             else:                                # beam rows: position j of row r lives in slot anc[r, j] (this step's own: anc[r, t] = r)
                 ops.attn_decode(_rows3(qkv[:, :D], B, H), ck, cv, _rows3(o, B, H), anc=st.anc)
             h = linear_fwd(o, w.sa.o, B, out_dtype=F32, residual=h)
+            lora_fwd(o, la.sa_o, h, B)
             q = linear_fwd(ln(h, lyr.encoder_attn_layer_norm), w.ca.q, B, flags=L.EPI_SCALE_N, scale=0.125, scale_ncols=D)
+            lora_fwd(x, la.ca_q, q, B, q_scale=0.125)
             if st.group == 1:
                 ops.attn_fwd(heads(q, B, 1, H), heads(c.ckv[:, :D], B, st.T, H), heads(c.ckv[:, D:], B, st.T, H), heads(o, B, 1, H))
             else:                                # the beams of a window share its cross-attention K/V
@@ -134,8 +137,11 @@ class GreedyDecoder:
                 ops.attn_decode(_rows3(q, B, H), heads(c.ckv[:, :D], B0, st.T, H), heads(c.ckv[:, D:], B0, st.T, H), _rows3(o, B, H),
                                 group=st.group)
             h = linear_fwd(o, w.ca.o, B, out_dtype=F32, residual=h)
-            a = linear_fwd(ln(h, lyr.final_layer_norm), w.fc1, B, flags=L.EPI_GELU)
+            lora_fwd(o, la.ca_o, h, B)
+            a = linear_fwd(ln(h, lyr.final_layer_norm), w.fc1, B, flags=0 if la.fc1 is not None else L.EPI_GELU)
+            lora_fwd(x, la.fc1, a, B, gelu=True)
             h = linear_fwd(a, w.fc2, B, out_dtype=F32, residual=h)
+            lora_fwd(a, la.fc2, h, B)
         logits = torch.empty(B, W.vpad, dtype=F32, device=dev)
         ops.gemm_nt(ln(h, dec.layer_norm), W.head.w, logits, B, W.vpad, D)
         return logits[:, :cfg.vocab_size]
@@ -177,8 +183,10 @@ class GreedyDecoder:
         for w, c in zip(W.layers, st.layers):
             if Bc == B0:
                 linear_fwd(enc_bf, w.ca.kv, B0 * T, out=c.ckv)
+                lora_fwd(enc_bf, w.lora.ca_kv, c.ckv, B0 * T)
             else:
                 kv = linear_fwd(enc_bf, w.ca.kv, B0 * T)
+                lora_fwd(enc_bf, w.lora.ca_kv, kv, B0 * T)
                 c.ckv.view(B0, num_beams, T, -1).copy_(kv.view(B0, 1, T, -1).expand(B0, num_beams, T, kv.shape[1]))
         return st
 

@@ -612,6 +612,7 @@ class DiCoWForConditionalGeneration(_ModelBase):
         self._ts_tables = None
         self._eng = None
         self._sig = None
+        self._lora_sig = None
         self.apply(self._init_weights)
         for m in self.modules():              # (HF's post_init / from_pretrained re-initialise whatever does not say it has been)
             m._is_hf_initialized = True
@@ -976,10 +977,17 @@ class DiCoWForConditionalGeneration(_ModelBase):
         if self._eng is None:
             self._eng = DecoderEngine(self)
         if prepare:
-            sig = _param_sig(list(self.model.decoder.parameters()))
+            # two signatures: a LoRA step moves only the adapters, and re-casting the frozen base weights and the LM head for it
+            # would cost more than the step's whole low-rank arithmetic -- only the adapters' bf16 copies are refreshed then
+            named = list(self.model.decoder.named_parameters())
+            sig = _param_sig([p for n, p in named if "lora_" not in n])
+            lsig = _param_sig([p for n, p in named if "lora_" in n])
             if sig != self._sig:
                 self._eng.prepare()
-                self._sig = sig
+                self._sig, self._lora_sig = sig, lsig
+            elif lsig != self._lora_sig:
+                self._eng.refresh_adapters()
+                self._lora_sig = lsig
         return self._eng
 
     def forward(self, input_features=None, attention_mask=None, stno_mask=None, decoder_input_ids=None,
@@ -1052,3 +1060,147 @@ def build_ts_tables(vocab, vocab_size, device, sigma=0.08):
     index = torch.full((max(vocab_size, int(ids.max()) + 1),), -1, dtype=torch.int32)
     index[ids.long()] = torch.arange(len(pairs), dtype=torch.int32)
     return {"ids": ids.to(device), "w": w.contiguous().to(device), "index": index.to(device)}
+
+
+# ------------------------------------------------------------------------------------------------ LoRA adapters on the decoder
+# reference src/models/containers.py:69-78: peft LoraConfig(r=16, lora_alpha=32, target_modules=<this regex>, lora_dropout=0.0, bias="none")
+LORA_TARGET_MODULES = r".*decoder.*(q_proj|k_proj|v_proj|out_proj|fc1|fc2).*"
+LORA_RANKS = (8, 16, 32, 64)                 # what the dicow_lora_* kernels take (include/dicow_hip.h)
+_LORA_LEAVES = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj", "encoder_attn.q_proj",
+                "encoder_attn.k_proj", "encoder_attn.v_proj", "encoder_attn.out_proj", "fc1", "fc2")
+
+
+class LoRALinear(nn.Linear):
+    """A decoder Linear with a rank-r adapter: y = W x + b + (alpha / r) B (A x).  ``weight`` / ``bias`` keep their state-dict keys;
+    the adapter's are ``lora_A.weight`` [r, in] and ``lora_B.weight`` [out, r] (peft's layout and initialisation: A kaiming-uniform
+    with a = sqrt(5), B zeros).  Like every module here it only HOLDS parameters: the arithmetic runs in engine.py (lora_fwd /
+    lora_bwd over dicow_lora_down / _up / _wgrad); ``forward`` is the plain fp32 restatement."""
+
+    def __init__(self, in_features, out_features, bias=True, r=16, lora_alpha=32, device=None, dtype=None):
+        super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
+        self.r, self.lora_alpha = int(r), float(lora_alpha)
+        self.lora_A = nn.Linear(in_features, self.r, bias=False, device=device, dtype=dtype)
+        self.lora_B = nn.Linear(self.r, out_features, bias=False, device=device, dtype=dtype)
+        nn.init.kaiming_uniform_(self.lora_A.weight, a=math.sqrt(5))
+        nn.init.zeros_(self.lora_B.weight)
+
+    @property
+    def scaling(self):
+        return self.lora_alpha / self.r
+
+    @classmethod
+    def from_linear(cls, base, r, lora_alpha):
+        m = cls(base.in_features, base.out_features, bias=base.bias is not None, r=r, lora_alpha=lora_alpha,
+                device=base.weight.device, dtype=base.weight.dtype)
+        m.weight, m.bias = base.weight, base.bias          # the SAME Parameter objects: ties, optimizer state and flat-store views survive
+        m.train(base.training)
+        return m
+
+    def forward(self, x):
+        return nn.functional.linear(x, self.weight, self.bias) + self.scaling * self.lora_B(self.lora_A(x))
+
+
+def _set_submodule(root, name, new):
+    parent_name, _, leaf = name.rpartition(".")
+    setattr(root.get_submodule(parent_name) if parent_name else root, leaf, new)
+
+
+def add_decoder_lora(model, r=16, lora_alpha=32, target_modules=LORA_TARGET_MODULES, lora_dropout=0.0, bias="none"):
+    """What ``get_peft_model(model, LoraConfig(...))`` does in the reference's container (containers.py:69-78), in place: every decoder
+    Linear whose module path fully matches ``target_modules`` (peft matches a string pattern with re.fullmatch) becomes a LoRALinear.
+    Base state-dict keys, ``_is_hf_initialized`` and the embedding / LM-head tie are untouched; requires_grad flags are left to the
+    freezing pass that follows in the container (trainer.freeze_by_keyword keeps ``lora_`` parameters trainable).  Returns the model."""
+    if lora_dropout != 0.0:
+        raise NotImplementedError("add_decoder_lora: lora_dropout != 0 is not implemented (the reference uses 0.0)")
+    if bias != "none":
+        raise NotImplementedError("add_decoder_lora: only bias='none' is implemented (the reference's setting)")
+    if int(r) not in LORA_RANKS:
+        raise ValueError(f"add_decoder_lora: rank {r} not in {LORA_RANKS} (the ranks the HIP kernels take)")
+    if not isinstance(target_modules, str):
+        raise TypeError("add_decoder_lora: target_modules is a regular expression over module paths, as in the reference")
+    pat = re.compile(target_modules)
+    hits = [(n, m) for n, m in model.named_modules() if isinstance(m, nn.Linear) and pat.fullmatch(n)]
+    if not hits:
+        raise ValueError(f"add_decoder_lora: {target_modules!r} matches no Linear")
+    for n, m in hits:
+        if not n.startswith("model.decoder.layers.") or n.split(".", 4)[-1] not in _LORA_LEAVES:
+            raise ValueError(f"add_decoder_lora: {target_modules!r} matches {n!r}: only the decoder layers' q/k/v/out projections and "
+                             "fc1 / fc2 can carry adapters")
+        if isinstance(m, LoRALinear):
+            raise ValueError(f"add_decoder_lora: {n!r} already carries an adapter")
+    for n, m in hits:
+        new = LoRALinear.from_linear(m, r, lora_alpha)
+        for sub in new.modules():
+            sub._is_hf_initialized = True
+        _set_submodule(model, n, new)
+    model._lora_config = dict(r=int(r), lora_alpha=float(lora_alpha), target_modules=target_modules, lora_dropout=0.0, bias="none")
+    model._sig = None                         # the engine rebuilds its weight set (adapter groups included) on the next call
+    model.tie_weights()
+    return model
+
+
+def lora_modules(model):
+    return [(n, m) for n, m in model.named_modules() if isinstance(m, LoRALinear)]
+
+
+def merge_lora(model):
+    """Fold s B A into the fp32 base weights and put plain nn.Linear modules back (peft's merge_and_unload).  Returns the model."""
+    for n, m in lora_modules(model):
+        with torch.no_grad():
+            m.weight.add_(m.scaling * (m.lora_B.weight.to(F32) @ m.lora_A.weight.to(F32)))
+        lin = nn.Linear(m.in_features, m.out_features, bias=m.bias is not None, device="meta")
+        lin.weight, lin.bias = m.weight, m.bias
+        lin.train(m.training)
+        lin._is_hf_initialized = True
+        _set_submodule(model, n, lin)
+    model._lora_config = None
+    model._sig = None
+    model.tie_weights()
+    return model
+
+
+def adapter_key(param_name):
+    """In-memory parameter name -> key in ``adapter_model.safetensors``.  peft stores ``base_model.model.<module path>.lora_A.weight``
+    (its in-memory ``.lora_A.default.weight`` with the adapter name removed).  UNVERIFIED against an installed peft: the naming is
+    kept in this one function."""
+    return "base_model.model." + param_name
+
+
+def save_adapter(model, directory):
+    """``adapter_model.safetensors`` (the lora_A / lora_B tensors) + ``adapter_config.json`` (peft's file names)."""
+    import json
+    import os
+    from safetensors.torch import save_file
+    cfg = getattr(model, "_lora_config", None)
+    if not cfg:
+        raise ValueError("save_adapter: the model carries no adapters (add_decoder_lora)")
+    os.makedirs(directory, exist_ok=True)
+    sd = {adapter_key(n): p.detach().cpu().contiguous() for n, p in model.named_parameters() if ".lora_A." in n or ".lora_B." in n}
+    save_file(sd, os.path.join(directory, "adapter_model.safetensors"), metadata={"format": "pt"})
+    with open(os.path.join(directory, "adapter_config.json"), "w") as f:
+        json.dump(dict(cfg, peft_type="LORA", task_type=None, fan_in_fan_out=False, inference_mode=False), f, indent=1)
+
+
+def load_adapter(model, directory):
+    """Reads what ``save_adapter`` wrote; attaches the adapters first when the model has none.  Every adapter tensor must be present."""
+    import json
+    import os
+    from safetensors.torch import load_file
+    with open(os.path.join(directory, "adapter_config.json")) as f:
+        cfg = json.load(f)
+    if not lora_modules(model):
+        add_decoder_lora(model, r=cfg["r"], lora_alpha=cfg["lora_alpha"], target_modules=cfg["target_modules"],
+                         lora_dropout=cfg.get("lora_dropout", 0.0), bias=cfg.get("bias", "none"))
+    sd = load_file(os.path.join(directory, "adapter_model.safetensors"))
+    own = {adapter_key(n): p for n, p in model.named_parameters() if ".lora_A." in n or ".lora_B." in n}
+    if set(own) != set(sd):
+        raise KeyError(f"load_adapter: adapter keys differ: missing {sorted(set(own) - set(sd))[:4]}, unexpected {sorted(set(sd) - set(own))[:4]}")
+    with torch.no_grad():
+        for k, p in own.items():
+            p.copy_(sd[k].to(device=p.device, dtype=p.dtype))
+    model._lora_sig = None
+    return model
+
+
+DiCoWForConditionalGeneration.save_adapter = save_adapter
+DiCoWForConditionalGeneration.load_adapter = load_adapter

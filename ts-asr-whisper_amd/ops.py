@@ -423,6 +423,84 @@ def attn_decode(q, k, v, o, *, group=1, anc=None):
     L.call_struct("dicow_attn_decode", a)
 
 
+# ------------------------------------------------------------------------------------------------ LoRA (dicow_lora_*)
+def _lora_2d(t, dtype, name):
+    _req(t, dtype, name)
+    assert t.dim() == 2 and t.stride(1) == 1, f"{name}: need a [rows, cols] view with unit column stride"
+    return t
+
+
+def lora_down(x, v, t, r, *, block=False):
+    """t[M, R] = x v^T (bf16).  Dense: x [M, K], v [R, K].  block: x [M, nseg * K] (nseg = R // r column segments), v [R, K], segment j is
+    contracted with rows [j r, (j + 1) r) of v.  x / v / t may be column slices (row strides are passed on)."""
+    for ten, n in ((x, "x"), (v, "v"), (t, "t")):
+        _lora_2d(ten, BF16, "lora_down." + n)
+    a = L.LoraDownArgs()
+    a.X, a.V, a.T = x.data_ptr(), v.data_ptr(), t.data_ptr()
+    a.ldx, a.ldv, a.ldt = x.stride(0), v.stride(0), t.stride(0)
+    a.M, a.K, a.R, a.r, a.flags = x.shape[0], v.shape[1], v.shape[0], int(r), L.LORA_BLOCK if block else 0
+    nseg = max(a.R // max(a.r, 1), 1) if block else 1
+    assert t.shape == (a.M, a.R) and x.shape[1] == nseg * a.K, "lora_down: shapes disagree"
+    L.call_struct("dicow_lora_down", a)
+    return t
+
+
+def lora_up(t, u, p, y, r, scales, *, block=False, gelu=False, mul_aux=False, aux=None):
+    """y = epi(p + bf16(s_j * bf16(t_j u_j))) (dicow_lora_up); y / p bf16 or fp32 [M, nseg * N] views (p may be y), t [M, R], u [R, N].
+    Dense: one contraction over all R columns of t, s = scales[0].  block: column segment j of y uses t[:, j r:(j + 1) r], rows
+    [j r, (j + 1) r) of u and scales[j].  gelu: y = gelu(bf16(sum)), aux (optional) receives gelu'.  mul_aux: p is fp32 (not y), y = bf16((p + v) * aux)."""
+    _lora_2d(t, BF16, "lora_up.t")
+    _lora_2d(u, BF16, "lora_up.u")
+    _lora_2d(y, y.dtype, "lora_up.y")
+    if y.dtype not in (BF16, F32):
+        raise L.DicowError(f"lora_up.y: expected bf16 or fp32, got {y.dtype}")
+    _lora_2d(p, F32 if mul_aux else y.dtype, "lora_up.p")
+    a = L.LoraUpArgs()
+    a.T, a.U, a.P, a.Y, a.aux = t.data_ptr(), u.data_ptr(), p.data_ptr(), y.data_ptr(), _p(aux)
+    a.ldt, a.ldu, a.ldp, a.ldy = t.stride(0), u.stride(0), p.stride(0), y.stride(0)
+    a.M, a.N, a.R, a.r = t.shape[0], u.shape[1], u.shape[0], int(r)
+    a.flags = (L.LORA_BLOCK if block else 0) | (L.LORA_OUT_F32 if y.dtype == F32 else 0) | (L.LORA_GELU if gelu else 0) | (L.LORA_MUL_AUX if mul_aux else 0)
+    nseg = max(a.R // max(a.r, 1), 1) if block else 1
+    assert t.shape[1] == a.R and y.shape == (a.M, nseg * a.N) and p.shape == y.shape, "lora_up: shapes disagree"
+    if aux is not None:
+        _lora_2d(aux, BF16, "lora_up.aux")
+        assert aux.shape == y.shape
+        a.ldaux = aux.stride(0)
+    scales = list(scales)
+    assert len(scales) >= nseg and nseg <= L.LORA_MAX_SEG, "lora_up: one scale per segment"
+    for j, s in enumerate(scales[:L.LORA_MAX_SEG]):
+        a.seg_scale[j] = float(s)
+    L.call_struct("dicow_lora_up", a)
+    return y
+
+
+def lora_wgrad(t, p, outs, r, scale, *, block=False, accumulate=True, g_rs=None, g_cs=1):
+    """outs[j] (+)= scale * t_j^T p_j, fp32; element (rho, n) of segment j at outs[j].data_ptr + rho * g_rs + n * g_cs (g_rs defaults to
+    N: a [r, N] destination; g_rs = 1, g_cs = r: an [N, r] one).  Dense: t [M, R], p [M, N], segment j = rows [j r, (j + 1) r) of
+    t^T p.  block: p [M, nseg * N], segment j = t[:, j r ..]^T p[:, j N ..].  A None entry of outs is skipped.  Deterministic."""
+    _lora_2d(t, BF16, "lora_wgrad.t")
+    _lora_2d(p, BF16, "lora_wgrad.p")
+    a = L.LoraWgradArgs()
+    a.T, a.P = t.data_ptr(), p.data_ptr()
+    a.ldt, a.ldp = t.stride(0), p.stride(0)
+    a.M, a.R, a.r, a.flags = t.shape[0], t.shape[1], int(r), L.LORA_BLOCK if block else 0
+    nseg = max(a.R // max(a.r, 1), 1)
+    assert p.shape[0] == a.M and len(outs) == nseg and nseg <= L.LORA_MAX_SEG, "lora_wgrad: shapes disagree"
+    a.N = p.shape[1] // nseg if block else p.shape[1]
+    assert not block or p.shape[1] == nseg * a.N
+    a.g_rs, a.g_cs = (a.N if g_rs is None else g_rs), g_cs
+    for j, g in enumerate(outs):
+        if g is not None:
+            _req(g, F32, "lora_wgrad.out")
+            assert g.is_contiguous() and g.numel() == a.r * a.N, "lora_wgrad.out: need a contiguous r x N (or N x r) fp32 tensor"
+            a.G[j] = g.data_ptr()
+    a.scale, a.accumulate = float(scale), int(bool(accumulate))
+    need = L.lib().dicow_lora_wgrad_ws_bytes(a.M, a.N, a.R, a.r, a.flags)
+    ws = workspace(max(need, 1), t.device)
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
+    L.call_struct("dicow_lora_wgrad", a)
+
+
 _FWS = {}
 ATTN_BWD_FUSED = os.environ.get("DICOW_ATTN_BWD_FUSED", "1") != "0"      # A/B switch of the fused (5-pass) attention backward
 

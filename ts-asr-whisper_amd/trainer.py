@@ -29,9 +29,9 @@ log = logging.getLogger(__name__)
 
 
 def freeze_by_keyword(model, frozen_keywords=("decoder",)):
-    """reference containers.py:80-90: requires_grad = not any(keyword in name)."""
+    """reference containers.py:80-90: requires_grad = "lora_" in name or not any(keyword in name)."""
     for n, p in model.named_parameters():
-        p.requires_grad_(not any(k in n for k in frozen_keywords))
+        p.requires_grad_("lora_" in n or not any(k in n for k in frozen_keywords))     # (containers.py:82-84: adapters always train)
     model.tie_weights()
 
 
@@ -624,6 +624,22 @@ class TrainStep:
         self.model.model.encoder._sig = None
         self.model._sig = None
 
+    def _invalidate_decoder_copies(self):
+        """After an optimizer step: the decoder's bf16 copies are stale when a base decoder parameter trains; when only LoRA adapters do
+        (frozen decoder + add_decoder_lora), only the adapters' copies are (DiCoWForConditionalGeneration._engine refreshes just those)."""
+        base = lora = False
+        for n, p in self.model.model.decoder.named_parameters():
+            if p.requires_grad:
+                if "lora_" in n:
+                    lora = True
+                else:
+                    base = True
+                    break
+        if base:
+            self.model._sig = None
+        elif lora:
+            self.model._lora_sig = None
+
     @property
     def global_step(self):
         return self.opt.t
@@ -654,8 +670,7 @@ class TrainStep:
         if not (self.warmup_phase and self._preheat_is_vectors_only):
             enc._sig = None
             enc._ctc_sig = None
-        if any(p.requires_grad for p in self.model.model.decoder.parameters()):
-            self.model._sig = None
+        self._invalidate_decoder_copies()
 
     def _micro(self, batch, scale):
         if self.split_streams and self._can_split(batch):
@@ -748,8 +763,7 @@ class TrainStep:
         enc = self.model.model.encoder
         enc._sig = None
         enc._ctc_sig = None
-        if any(p.requires_grad for p in self.model.model.decoder.parameters()):
-            self.model._sig = None
+        self._invalidate_decoder_copies()
 
     def _graph_step(self, batch):
         if self.reducer.world > 1 or self.reducer.force:
