@@ -498,6 +498,22 @@ int dicow_whisper_timestamp_rules(float* scores, int64_t ld, int B, int V, const
                                   int timestamp_begin, int eos, int no_timestamps, int max_initial_timestamp_index,
                                   int detect_from_logprob, void* stream);
 
+/* Repetition penalty and no-repeat n-grams on next-token scores, in place (ABI 7, additive): transformers'
+ * RepetitionPenaltyLogitsProcessor followed by NoRepeatNGramLogitsProcessor, the two processors HF's generate -- which the
+ * reference's delegates to -- builds from generation_config.repetition_penalty / .no_repeat_ngram_size
+ * (src/utils/general.py:19-34) and runs in front of Whisper's own.
+ * scores fp32 [rows, ld >= V]; row r's history (prompt + tokens generated so far) is the L >= 1 int64 entries at
+ * input_ids + r * ids_stride (ids_stride >= L, L <= 8192).
+ *   penalty (> 0; 1 = off): every DISTINCT history token v gets s = scores[r, v] <- s < 0 ? s * penalty : s / penalty, once however
+ *     often it occurs (-inf stays -inf, -0.0 is divided);
+ *   ngram (<= 0 = off): if L + 1 >= ngram, for every j in [0, L - ngram] with ids[j .. j + ngram - 2] equal to the last
+ *     ngram - 1 entries of the history, scores[r, ids[j + ngram - 1]] <- -inf (ngram == 1: every history token); a token that is
+ *     penalised and banned ends as -inf.
+ * An id outside [0, V) takes part in the n-gram comparison by value but never indexes the scores.  Columns >= V and rows >= rows
+ * are not touched.  One launch, no workspace, deterministic; with both rules off nothing is launched. */
+int dicow_repetition_rules(float* scores, int64_t ld, int rows, int V, const int64_t* input_ids, int64_t ids_stride, int L,
+                           float penalty, int ngram, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ optimizer
  * Fused AdamW + global-norm clipping on flat fp32 regions (src/models/containers.py:100-114 two param groups;
  * HF Trainer max_grad_norm 1.0).  dicow_sumsq_f32 accumulates sum(x^2) into out[0], DETERMINISTICALLY for a given input

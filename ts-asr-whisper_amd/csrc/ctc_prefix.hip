@@ -269,3 +269,67 @@ extern "C" int dicow_whisper_timestamp_rules(float* scores, int64_t ld, int B, i
     DICOW_CHECK_LAUNCH("timestamp_rules_kernel");
     return DICOW_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ repetition rules
+// transformers' RepetitionPenaltyLogitsProcessor followed by NoRepeatNGramLogitsProcessor on one row of next-token scores (HF
+// gathers / scatters over the history for the first and walks a Python dict of n-grams per row on the host for the second).
+// One workgroup per row: the history is staged once in LDS as int32 (-1 for an id outside [0, V): such an id never indexes the
+// row); the thread that owns the FIRST occurrence of a token applies the penalty, so every score has one writer and a token seen
+// three times is penalised once; after a workgroup barrier the thread of every earlier occurrence of the last ngram - 1 tokens
+// bans the token that followed it.  A ban over a penalised score is ordered by that barrier; concurrent bans of one token store
+// the same -inf.  No atomics, no workspace: the result is a function of the inputs alone.
+#define RPT_BLOCK 512
+#define RPT_MAX_L 8192      // 32 KB of LDS; Whisper's max_target_positions is 448
+__global__ void __launch_bounds__(RPT_BLOCK) repetition_rules_kernel(float* __restrict__ scores, int64_t ld, int V,
+                                                                     const int64_t* __restrict__ ids, int64_t ids_stride, int L,
+                                                                     float penalty, int ngram) {
+    extern __shared__ __attribute__((aligned(16))) int rpt_hist[];     // [(L + 3) & ~3]
+    const int tid = threadIdx.x;
+    float* row = scores + (int64_t)blockIdx.x * ld;
+    const int64_t* seq = ids + (int64_t)blockIdx.x * ids_stride;
+    const int L4 = (L + 3) & ~3;
+    for (int j = tid; j < L4; j += RPT_BLOCK) {
+        const int64_t v = j < L ? seq[j] : -1;
+        rpt_hist[j] = (v >= 0 && v < V) ? (int)v : -1;
+    }
+    __syncthreads();
+    if (penalty != 1.f) {
+        for (int j = tid; j < L; j += RPT_BLOCK) {
+            const int v = rpt_hist[j];
+            if (v < 0) continue;
+            bool seen = false;                            // does v occur in [0, j)?  (all lanes read the same words: LDS broadcast)
+            for (int i = 0; i < j; i += 4) {
+                const int4 h = *reinterpret_cast<const int4*>(rpt_hist + i);
+                seen |= (h.x == v) | (h.y == v && i + 1 < j) | (h.z == v && i + 2 < j) | (h.w == v && i + 3 < j);
+            }
+            if (seen) continue;
+            const float s = row[v];
+            row[v] = s < 0.f ? s * penalty : s / penalty;
+        }
+    }
+    if (ngram <= 0 || L + 1 < ngram) return;              // (uniform over the workgroup)
+    __syncthreads();
+    const int m = ngram - 1, tail = L - m;                // the last m tokens start at `tail`
+    for (int j = tid; j + ngram <= L; j += RPT_BLOCK) {
+        const int v = rpt_hist[j + m];
+        if (v < 0) continue;
+        bool same = true;
+        for (int k = 0; k < m && same; ++k) {
+            const int a = rpt_hist[j + k];
+            same = a == rpt_hist[tail + k] && (a >= 0 || seq[j + k] == seq[tail + k]);     // out-of-range ids compare by value
+        }
+        if (same) row[v] = -INFINITY;
+    }
+}
+
+extern "C" int dicow_repetition_rules(float* scores, int64_t ld, int rows, int V, const int64_t* input_ids, int64_t ids_stride, int L,
+                                      float penalty, int ngram, void* stream) {
+    DICOW_REQUIRE(scores && input_ids && rows > 0 && V > 0 && ld >= V && L >= 1 && L <= RPT_MAX_L && ids_stride >= L,
+                  "repetition_rules: bad args rows=%d V=%d ld=%lld L=%d ids_stride=%lld", rows, V, (long long)ld, L, (long long)ids_stride);
+    DICOW_REQUIRE(penalty > 0.f, "repetition_rules: penalty %g is not > 0", (double)penalty);
+    if (penalty == 1.f && ngram <= 0) return DICOW_OK;    // both rules off: nothing to launch
+    const size_t lds = (size_t)((L + 3) & ~3) * sizeof(int);
+    repetition_rules_kernel<<<rows, RPT_BLOCK, lds, (hipStream_t)stream>>>(scores, ld, V, input_ids, ids_stride, L, penalty, ngram);
+    DICOW_CHECK_LAUNCH("repetition_rules_kernel");
+    return DICOW_OK;
+}

@@ -10,6 +10,8 @@ Mirrors, for the in-training evaluation the reference runs every ``eval_steps``:
                             finished rows are padded, decoding stops when every row has produced eos.
 
   * ``timestamp_rules``     WhisperTimeStampLogitsProcessorCustom (src/models/dicow/utils.py:5-14) as one kernel per step;
+  * ``repetition_rules``    transformers' RepetitionPenaltyLogitsProcessor + NoRepeatNGramLogitsProcessor (generation_config
+                            .repetition_penalty / .no_repeat_ngram_size) as one kernel per step, first in the chain as in HF;
   * joint CTC / attention   ``ctc=dict(...)`` switches on ctc_decoding.CtcRescorer (decoding.py) after a log-softmax, as the
                             reference wires it for greedy search (generation.py:249-268).
 
@@ -52,6 +54,42 @@ def timestamp_rules(input_ids, scores, begin_index, eos_token_id, no_timestamps_
     L.call("dicow_whisper_timestamp_rules", scores.data_ptr(), scores.stride(0), B, V, ids.data_ptr(), ids.shape[1], begin_index,
            no_timestamps_token_id + 1, eos_token_id, no_timestamps_token_id,
            -1 if max_initial_timestamp_index is None else max_initial_timestamp_index, int(detect_from_logprob), L.stream())
+    return scores
+
+
+def repetition_options(repetition_penalty=None, no_repeat_ngram_size=None):
+    """Validation of transformers' two processors: (penalty, ngram) as the kernel takes them, or None when both are off
+    (None, penalty 1.0 and n-gram size 0 mean off, as in HF's _get_logits_processor)."""
+    penalty, ngram = 1.0, 0
+    if repetition_penalty is not None and repetition_penalty != 1.0:
+        if not isinstance(repetition_penalty, float) or not repetition_penalty > 0:
+            raise ValueError(f"`penalty` has to be a strictly positive float, but is {repetition_penalty}")
+        penalty = repetition_penalty
+    if no_repeat_ngram_size is not None and no_repeat_ngram_size != 0:
+        if isinstance(no_repeat_ngram_size, bool) or not isinstance(no_repeat_ngram_size, int) or no_repeat_ngram_size <= 0:
+            raise ValueError(f"`ngram_size` has to be a strictly positive integer, but is {no_repeat_ngram_size}")
+        ngram = no_repeat_ngram_size
+    return None if (penalty == 1.0 and ngram == 0) else (penalty, ngram)
+
+
+def repetition_rules(input_ids, scores, repetition_penalty=None, no_repeat_ngram_size=None):
+    """transformers' RepetitionPenaltyLogitsProcessor, then NoRepeatNGramLogitsProcessor (what HF's generate builds from
+    generation_config.repetition_penalty / .no_repeat_ngram_size and runs in front of Whisper's processors): scores fp32 [B, V]
+    on the GPU are changed IN PLACE (and returned); input_ids int64 [B, L] = prompt + generated tokens, rows may be slices of a
+    wider buffer.  With both options off nothing is launched."""
+    opt = repetition_options(repetition_penalty, no_repeat_ngram_size)
+    if not scores.is_cuda or scores.dtype != F32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise L.DicowError("repetition_rules: scores must be fp32 rows on the GPU (no CPU fallback)")
+    if opt is None:
+        return scores
+    ids = input_ids.to(device=scores.device, dtype=torch.int64)
+    if ids.dim() != 2 or ids.shape[0] != scores.shape[0]:
+        raise L.DicowError("repetition_rules: input_ids must be [rows, L] with one row per row of scores")
+    if ids.stride(1) != 1 or ids.stride(0) < ids.shape[1]:
+        ids = ids.contiguous()
+    B, V = scores.shape
+    L.call("dicow_repetition_rules", scores.data_ptr(), scores.stride(0), B, V, ids.data_ptr(), ids.stride(0), ids.shape[1],
+           opt[0], opt[1], L.stream())
     return scores
 
 
@@ -211,12 +249,13 @@ class GreedyDecoder:
     @torch.no_grad()
     def beam_search(self, input_features, stno_mask, decoder_input_ids, max_length, num_beams, eos_token_id=None, pad_token_id=None,
                     length_penalty=1.0, early_stopping=False, suppress_tokens=None, begin_suppress_tokens=None, enrollments=None,
-                    timestamps=None, ctc=None, reorder_caches=False):
+                    timestamps=None, ctc=None, reorder_caches=False, repetition_penalty=None, no_repeat_ngram_size=None):
         """Beam search as the reference runs it (DiCoWGenerationMixin._beam_search, generation.py:815-1153, on transformers'
         vectorised beam helpers): per step the top 2K continuations over beams x vocabulary, the K best unfinished keep running,
         finished ones compete for the K result slots with length-penalised scores; processors act on log-probabilities
         (suppress lists, timestamp rules, joint CTC term without a second log-softmax, generation.py:249-268); KV caches and
-        the CTC states follow ``beam_idx``.  Returns (sequences [B, <= max_length], scores [B]) of the best hypothesis.
+        the CTC states follow ``beam_idx``.  repetition_penalty / no_repeat_ngram_size: ``repetition_rules`` on the log-probabilities,
+        first in the chain (where HF's beam search applies its processors).  Returns (sequences [B, <= max_length], scores [B]) of the best hypothesis.
 
         The caches follow their beams WITHOUT being copied: a window's cross-attention K/V exist once and are read by its K
         rows (ops.attn_decode, group=K); every row writes its self-attention key / value into its own slot and reads position j
@@ -229,6 +268,7 @@ class GreedyDecoder:
         eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
         pad = cfg.pad_token_id if pad_token_id is None else pad_token_id
         reorder_caches = bool(reorder_caches) or K > L.ATTN_DECODE_MAX_GROUP
+        rep = repetition_options(repetition_penalty, no_repeat_ngram_size)
         if self.use_graphs and (reorder_caches or K == 1):           # (one beam: no indirect state; refused under graphs as before)
             raise L.DicowError("beam_search(reorder_caches=True) (also: more than %d beams) copies the KV caches every step: use a "
                                "decoder without graph capture" % L.ATTN_DECODE_MAX_GROUP)
@@ -275,6 +315,8 @@ class GreedyDecoder:
         while True:
             flat = run_seq[:, :, :cur].reshape(B * K, cur)
             logp = torch.log_softmax(step(flat[:, -1].contiguous(), cur - 1, st).float(), dim=-1)
+            if rep is not None:
+                logp = repetition_rules(flat, logp, *rep)
             if sup is not None:
                 logp[:, sup] = -float("inf")
             if bsup is not None and cur == P:
@@ -324,12 +366,15 @@ class GreedyDecoder:
     @torch.no_grad()
     def generate(self, input_features, stno_mask, decoder_input_ids, max_new_tokens, eos_token_id=None, pad_token_id=None,
                  suppress_tokens=None, begin_suppress_tokens=None, enrollments=None, return_scores=False, ctc=None,
-                 timestamps=None, temperature=0.0, generator=None, no_speech_token_id=None):
+                 timestamps=None, temperature=0.0, generator=None, no_speech_token_id=None, repetition_penalty=None,
+                 no_repeat_ngram_size=None):
         """decoder_input_ids int64 [B, P]: the forced prefix (start token, language / task / timestamp tokens).
         ctc: dict(weight=..., first_timestamp=..., upper_cased=[(lo, up), ...], prefix_len=..., n_score=500) switches on the
         joint CTC / attention scoring of generation.py:249-268 (log-softmax, then ctc_decoding.CtcRescorer on the model's CTC head).
         timestamps: dict(no_timestamps_token_id=..., max_initial_timestamp_index=...) applies Whisper's timestamp rules
         (return_timestamps=True in the reference, generation.py:272-281), after the suppress lists and before the CTC term.
+        repetition_penalty / no_repeat_ngram_size: ``repetition_rules`` on the step's raw logits, before the suppress lists (HF's
+        order: its own processors run in front of Whisper's).
         temperature > 0: multinomial sampling from softmax(processed scores / temperature) (HF's sample mode, what Whisper's
         temperature fallback decodes with; `generator` makes it reproducible); the returned scores are then the temperature-scaled
         ones, as HF's are.  no_speech_token_id: also keep softmax(logits of the position after the start token)[that id] per row
@@ -353,6 +398,7 @@ class GreedyDecoder:
             rescorer = CtcRescorer(enc_logits, cfg.vocab_size, eos, ids[0, 0].item(), ctc["first_timestamp"], ctc.get("upper_cased", ()),
                                    ctc.get("prefix_len", P), ctc["weight"], ctc.get("n_score", 500))
             rows = torch.arange(B, device=dev)
+        rep = repetition_options(repetition_penalty, no_repeat_ngram_size)
         step = self._step_graphed if self.use_graphs else self._step
         self.no_speech_prob = None
         for t in range(P - 1):                                       # prefill the caches with the prefix
@@ -366,6 +412,8 @@ class GreedyDecoder:
             logits = step(cur, P - 1 + n, st)
             if n == 0 and P == 1 and no_speech_token_id is not None:
                 self.no_speech_prob = torch.softmax(logits.float(), dim=-1)[:, no_speech_token_id].clone()
+            if rep is not None:
+                logits = repetition_rules(torch.cat(seq, dim=1), logits, *rep)
             if sup is not None:
                 logits[:, sup] = -float("inf")
             if bsup is not None and n == 0:
@@ -402,7 +450,7 @@ class GreedyDecoder:
         generate_with_fallback): greedy first; windows whose output is too repetitive (zlib compression ratio) or too unlikely
         (average log-probability) are decoded again -- encoder included, as in HF -- with sampling at the next temperature; a
         window that is unlikely AND looks like silence (no_speech_prob) is skipped instead.  gen_kw: generate()'s processor
-        arguments (eos / pad ids, suppress lists, timestamps, ctc).
+        arguments (eos / pad ids, suppress lists, timestamps, ctc, repetition_penalty, no_repeat_ngram_size).
         Returns (token lists of the generated positions without the eos, should_skip flags, temperature index per window)."""
         cfg = self.cfg
         eos = gen_kw.get("eos_token_id", None)
@@ -648,7 +696,8 @@ class LongFormDecoder:
                    pad_token_id=None, max_new_tokens=None, enrollments=None, **gen_kw):
         """input_features [B, M, T_total] (T_total a multiple of nothing in particular), stno_mask [B, 4, T_total / 2],
         max_frames [B] valid feature frames per recording, decoder_input_ids [1 or B, P] the forced prompt.
-        gen_kw: suppress_tokens, begin_suppress_tokens, max_initial_timestamp_index, ctc, the fallback arguments, and for
+        gen_kw: suppress_tokens, begin_suppress_tokens, max_initial_timestamp_index, ctc, repetition_penalty and
+        no_repeat_ngram_size (every window's history starts from that window's prompt, as in HF), the fallback arguments, and for
         num_beams > 1 length_penalty, early_stopping and reorder_caches (False: beam_search's default beam-indirect caches; True: its
         former copying path).
         Returns per recording a list of segments dict(start, end, tokens) in seconds / token ids."""
@@ -678,7 +727,8 @@ class LongFormDecoder:
                       timestamps=dict(no_timestamps_token_id=no_timestamps_token_id,
                                       max_initial_timestamp_index=gen_kw.get("max_initial_timestamp_index", 50)),
                       suppress_tokens=gen_kw.get("suppress_tokens"), begin_suppress_tokens=gen_kw.get("begin_suppress_tokens"),
-                      ctc=gen_kw.get("ctc"))
+                      ctc=gen_kw.get("ctc"), repetition_penalty=gen_kw.get("repetition_penalty"),
+                      no_repeat_ngram_size=gen_kw.get("no_repeat_ngram_size"))
             skip = [False] * len(active)
             if gen_kw.get("temperatures") is not None and self.num_beams == 1:
                 # temperature fallback (reference generation.py:567-611): per-window ladder, silent windows skipped

@@ -732,7 +732,8 @@ class DiCoWForConditionalGeneration(_ModelBase):
         Longer recordings, and one window WITH timestamp prediction: the seek loop of HF's / the reference's generate
         (generation.LongFormDecoder) and the window-relative sequences of _fix_timestamps_from_segmentation.
         ``generation_config``: any object with the HF / reference attribute names (eos_token_id, pad_token_id, suppress_tokens,
-        begin_suppress_tokens, return_timestamps, no_timestamps_token_id, max_initial_timestamp_index, ctc_weight, ...).
+        begin_suppress_tokens, return_timestamps, no_timestamps_token_id, max_initial_timestamp_index, ctc_weight,
+        repetition_penalty, no_repeat_ngram_size, ...).
         The prompt is ``decoder_input_ids`` or [decoder_start_token_id] + the tokenizer's prefix tokens."""
         from .generation import GreedyDecoder
         gc = generation_config if generation_config is not None else self.generation_config
@@ -773,14 +774,19 @@ class DiCoWForConditionalGeneration(_ModelBase):
         # that ends in an open timestamp gets a second pass over its tail, and the return value is the segment-derived matrix of
         # _fix_timestamps_from_segmentation.  With timestamps on and a real tokenizer set (the fix-up needs its ids) a
         # one-window input therefore takes the same path as a long recording; all of its frames count as valid by default.
+        # HF's own two history processors (generation.repetition_rules), first in the chain on every path; validated here so that a
+        # bad value raises before any window is decoded
+        from .generation import repetition_options
+        rep_kw = dict(repetition_penalty=get("repetition_penalty"), no_repeat_ngram_size=get("no_repeat_ngram_size"))
+        repetition_options(**rep_kw)
         if one_window and ts_on and hasattr(self.tokenizer, "get_vocab"):
             if attention_mask is None:
                 attention_mask = torch.ones(input_features.shape[0], input_features.shape[-1], dtype=torch.long, device=input_features.device)
             return self._generate_long_form(input_features, stno_mask, attention_mask, decoder_input_ids, max_new_tokens, get, beams,
-                                            enrollments, gc)
+                                            enrollments, gc, rep_kw)
         if input_features.shape[-1] > 2 * cfg.max_source_positions:
             return self._generate_long_form(input_features, stno_mask, attention_mask, decoder_input_ids, max_new_tokens, get, beams,
-                                            enrollments, gc)
+                                            enrollments, gc, rep_kw)
         if input_features.shape[-1] != 2 * cfg.max_source_positions:
             raise ValueError("input_features shorter than one window: pad the features to 2 * max_source_positions frames")
         B = input_features.shape[0]
@@ -817,7 +823,7 @@ class DiCoWForConditionalGeneration(_ModelBase):
                                      eos_token_id=get("eos_token_id", cfg.eos_token_id), pad_token_id=get("pad_token_id", cfg.pad_token_id),
                                      length_penalty=get("length_penalty", 1.0), early_stopping=get("early_stopping", False),
                                      suppress_tokens=get("suppress_tokens"), begin_suppress_tokens=get("begin_suppress_tokens"),
-                                     enrollments=enrollments, timestamps=timestamps, ctc=ctc)
+                                     enrollments=enrollments, timestamps=timestamps, ctc=ctc, **rep_kw)
             return seq
         dec = self._decoder
         if use_graphs:                                       # hipGraph replay of each decoder position (evaluation: fixed weights)
@@ -827,7 +833,7 @@ class DiCoWForConditionalGeneration(_ModelBase):
         return dec.generate(input_features, stno_mask, decoder_input_ids, max_new_tokens,
                                       eos_token_id=get("eos_token_id", cfg.eos_token_id), pad_token_id=get("pad_token_id", cfg.pad_token_id),
                                       suppress_tokens=get("suppress_tokens"), begin_suppress_tokens=get("begin_suppress_tokens"),
-                                      enrollments=enrollments, ctc=ctc, timestamps=timestamps)
+                                      enrollments=enrollments, ctc=ctc, timestamps=timestamps, **rep_kw)
 
     def retrieve_init_tokens(self, input_features, stno_mask, generation_config, enrollments=None, return_timestamps=None):
         """The forced prompt per row the way the reference's evaluation gets it (DiCoWGenerationMixin._retrieve_init_tokens,
@@ -877,7 +883,7 @@ class DiCoWForConditionalGeneration(_ModelBase):
         return torch.tensor([[start, l] + tail for l in langs], dtype=torch.long)
 
     def _generate_long_form(self, input_features, stno_mask, attention_mask, decoder_input_ids, max_new_tokens, get, beams, enrollments,
-                            gc=None):
+                            gc=None, rep_kw=None):
         """Recordings longer than one window (reference generate(), generation.py:536-564, with HF's seek loop underneath):
         sequential windows at temperature 0 with timestamps, segments per recording, and -- what the reference returns for
         such inputs -- the window-relative token sequences of ``_fix_timestamps_from_segmentation`` (padded LongTensor).  The
@@ -914,7 +920,7 @@ class DiCoWForConditionalGeneration(_ModelBase):
                               enrollments=enrollments, suppress_tokens=get("suppress_tokens"),
                               begin_suppress_tokens=get("begin_suppress_tokens"),
                               max_initial_timestamp_index=get("max_initial_timestamp_index", 50),
-                              length_penalty=get("length_penalty", 1.0), early_stopping=get("early_stopping", False), ctc=ctc, **fb)
+                              length_penalty=get("length_penalty", 1.0), early_stopping=get("early_stopping", False), ctc=ctc, **fb, **(rep_kw or {}))
         self.last_segments = segs
         pad_id = getattr(tok, "pad_token_id", None)
         return fix_timestamps_from_segmentation(segs, first_ts, vocab["\u0120"], cfg.pad_token_id if pad_id is None else pad_id,
