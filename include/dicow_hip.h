@@ -514,6 +514,20 @@ int dicow_whisper_timestamp_rules(float* scores, int64_t ld, int B, int V, const
 int dicow_repetition_rules(float* scores, int64_t ld, int rows, int V, const int64_t* input_ids, int64_t ids_stride, int L,
                            float penalty, int ngram, void* stream);
 
+/* Greedy CTC decoding (ABI 7, additive): ctc_greedy_decode of the reference (src/utils/decoding.py:6-12: torch.argmax, then a Python
+ * itertools.groupby over every row of the device tensor), the preprocess_logits_for_metrics of CTC pre-training (src/pretrain_encoder.py:82-86).
+ * logits fp32 / bf16 (in_bf16): frame t of batch row b starts at element b * batch_stride + t * ld; unit stride over the V1 <= ld classes.  The
+ * base pointer needs the alignment of its element type only.
+ * out int64: out[b * out_stride + j], j < n_b, is the frame-wise argmax path of row b with consecutive repeats merged and every id equal
+ * to `blank` dropped; out[b * out_stride + j] = pad_id for n_b <= j < Tn (out_stride >= Tn; nothing else is written).
+ * The argmax is over columns < V1 only -- columns [V1, ld) are never read -- and on equal maxima the lowest index wins (torch.argmax on the
+ * CPU); +-inf follow the same rule, a row of -inf gives 0.  NaN among the V1 columns is outside the contract (the id still lies in [0, V1)).
+ * blank and pad_id are arbitrary: an id that never occurs drops nothing, pad_id may be negative.
+ * ws: int32 [B * Tn] workspace of the caller (the frame-wise argmax).  B * Tn < 2^31.  Two launches, no host read, no atomics: the result
+ * is a function of the inputs alone, and the call can be captured into a graph. */
+int dicow_ctc_greedy_decode(const void* logits, int in_bf16, int64_t batch_stride, int64_t ld, int B, int Tn, int V1, int64_t blank,
+                            int64_t pad_id, int* ws, int64_t* out, int64_t out_stride, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ optimizer
  * Fused AdamW + global-norm clipping on flat fp32 regions (src/models/containers.py:100-114 two param groups;
  * HF Trainer max_grad_norm 1.0).  dicow_sumsq_f32 accumulates sum(x^2) into out[0], DETERMINISTICALLY for a given input

@@ -11,13 +11,79 @@ of small torch tensor ops on [B, V]; states are kept for the scored candidates o
 scatters them into a [B, V, T, 2] buffer.  Everything stays on the device with fixed shapes (finished rows are scored
 and then masked instead of being filtered out); after the first call, which inspects the prompt layout, a decoding step adds
 no host synchronisation.  No CPU fallback.
+
+Greedy CTC decoding, the evaluation half of CTC pre-training (reference src/pretrain_encoder.py, src/utils/trainers.py:31-103):
+  * ``ctc_greedy_decode``   src/utils/decoding.py:6-12 (argmax + a Python groupby per row) as two kernels (csrc/ctc_greedy.hip);
+  * ``chunked_ctc_logits``  the windowing of CustomTrainerEncoder.prediction_step (trainers.py:54-63) without its concatenation.
 """
 import torch
 
 from . import _lib as L
 
-F32, BF16, I32 = torch.float32, torch.bfloat16, torch.int32
+F32, BF16, I32, I64 = torch.float32, torch.bfloat16, torch.int32, torch.int64
 LOGZERO = -1e10
+
+
+def ctc_greedy_decode(logits, blank, pad_token_id, *, out=None):
+    """logits [B, Tn, V1] on the GPU -> int64 [B, Tn]: per row the argmax path with consecutive repeats merged and ``blank`` dropped,
+    padded with ``pad_token_id`` (the reference's function of the same name and positional signature; ties go to the lowest index).
+    fp32 / bf16 logits with unit last stride are read in place, whatever their row and batch strides -- the 128-padded bf16 view that
+    ``encoder(..., return_logits=True).logits`` and ``chunked_ctc_logits`` return included; anything else is copied first.
+    ``out``: an int64 [B, Tn] tensor (unit last stride, any row stride >= Tn) to write instead of a new one.
+    Two launches on the current stream, no host read: the call can be captured into a graph."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+        raise L.DicowError("ctc_greedy_decode: logits must be on the GPU (no CPU fallback)")
+    if logits.dim() != 3:
+        raise L.DicowError(f"ctc_greedy_decode: expected logits [B, Tn, V1], got {tuple(logits.shape)}")
+    B, Tn, V1 = logits.shape
+    if out is None:
+        out = torch.empty(B, Tn, dtype=I64, device=logits.device)
+    elif (out.dtype != I64 or out.device != logits.device or tuple(out.shape) != (B, Tn) or (Tn > 1 and out.stride(1) != 1)
+          or (B > 1 and out.stride(0) < Tn)):
+        raise L.DicowError(f"ctc_greedy_decode: out must be an int64 [{B}, {Tn}] tensor on {logits.device} with unit last stride")
+    if B == 0 or Tn == 0:
+        return out
+    if V1 == 0:
+        raise L.DicowError("ctc_greedy_decode: no classes")
+    if logits.dtype not in (F32, BF16):
+        logits = logits.float()
+    in_place = logits.stride(2) == 1 or V1 == 1
+    in_place = in_place and (Tn == 1 or logits.stride(1) >= V1) and (B == 1 or logits.stride(0) >= 0)
+    if not in_place:
+        logits = logits.contiguous()
+    ld = logits.stride(1) if Tn > 1 else V1
+    bs = logits.stride(0) if B > 1 else 0
+    ws = torch.empty(B * Tn, dtype=I32, device=logits.device)
+    L.call("dicow_ctc_greedy_decode", logits.data_ptr(), int(logits.dtype == BF16), bs, ld, B, Tn, V1, int(blank), int(pad_token_id),
+           ws.data_ptr(), out.data_ptr(), out.stride(0) if B > 1 else Tn, L.stream())
+    return out
+
+
+def chunked_ctc_logits(encoder, input_features, stno_mask=None):
+    """CTC logits of a recording longer than one encoder window, as CustomTrainerEncoder.prediction_step forms them
+    (src/utils/trainers.py:54-63): the last dimension of ``input_features`` is cut into windows of ``encoder.get_max_len()`` frames,
+    every window runs through the encoder and its CTC head, and the logits stand side by side -> [B, n_win * Tn, V1].  Each window's
+    logits are written straight into one preallocated buffer of 128-padded bf16 rows (the reference concatenates); the returned
+    view feeds ``encoder.get_loss`` and ``ctc_greedy_decode`` without a copy.  ``stno_mask`` [B, 4, frames / 2] (optional when the
+    encoder has no FDDT) is cut the same way.  A length that is not a whole number of windows raises, as the encoder does for a short
+    window.  Inference only: nothing is kept for a backward pass, so the call must run under ``torch.no_grad()``."""
+    if torch.is_grad_enabled():
+        raise L.DicowError("chunked_ctc_logits is inference only: call it under torch.no_grad()")
+    if not input_features.is_cuda:
+        raise L.DicowError("chunked_ctc_logits: tensors must be on the GPU (no CPU fallback)")
+    win = encoder.get_max_len()
+    length = input_features.shape[-1]
+    if length == 0 or length % win != 0:
+        raise ValueError(f"Whisper expects the mel input features to be of length {win}, but found a last window of {length % win} frames "
+                         f"({length} in all). Make sure to pad the input mel features to a multiple of {win}.")
+    n_win = length // win
+    B, V1 = input_features.shape[0], encoder.config.vocab_size + 1
+    Tn, cpad = encoder.ctc_logits_layout()
+    buf = torch.empty(B, n_win * Tn, cpad, dtype=BF16, device=input_features.device)
+    for w in range(n_win):
+        st = None if stno_mask is None else stno_mask[..., w * (win // 2):(w + 1) * (win // 2)]
+        encoder.ctc_logits_into(input_features[..., w * win:(w + 1) * win], st, buf[:, w * Tn:(w + 1) * Tn])
+    return buf[:, :, :V1]
 
 
 def log_softmax_scores(scores):

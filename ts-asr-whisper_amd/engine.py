@@ -1532,6 +1532,10 @@ class CtcEngine:
         self.W = W
         return W
 
+    def frames(self, T):
+        """CTC frames the head makes of T encoder frames (two stride-2 convolutions under pre_ctc_sub_sample)."""
+        return T // 4 if hasattr(self.enc, "subsample_conv1") else T
+
     def forward(self, enc_bf, B, T, labels, enc_f32=None):
         cfg, W = self.cfg, self.W
         dev = enc_bf.device
@@ -1551,9 +1555,11 @@ class CtcEngine:
             raise L.DicowError("only ctc_loss_reduction='mean' (reference default) is implemented")
         return S.acc[0] / B, S
 
-    def encode_logits(self, enc_bf, B, T, enc_f32=None):
+    def encode_logits(self, enc_bf, B, T, enc_f32=None, out=None):
         """The CTC branch up to its logits (encoder.py:87-106, get_enc_logits): S.logits bf16 [B * Tn, cpad].
-        enc_f32: the fp32 rows enc_bf was rounded from (the residual stream of ``additional_layer``)."""
+        enc_f32: the fp32 rows enc_bf was rounded from (the residual stream of ``additional_layer``).
+        out (inference): a bf16 [B, Tn, cpad] view with any batch stride that receives the logits instead (one window of a longer
+        recording inside the buffer of all its windows); S.logits is that view."""
         enc, cfg, W = self.enc, self.cfg, self.W
         dev = enc_bf.device
         D, H = cfg.d_model, cfg.encoder_attention_heads
@@ -1598,6 +1604,12 @@ class CtcEngine:
             S.hpad, S.c1pad, S.T1 = hpad, c1pad, T1
             Tn = T2
         S.h, S.Tn = h, Tn
+        if out is not None:
+            if out.dtype != BF16 or tuple(out.shape) != (B, Tn, W.cpad) or out.stride(2) != 1 or out.stride(1) != W.cpad or out.stride(0) < Tn * W.cpad:
+                raise L.DicowError(f"encode_logits: out must be a bf16 [{B}, {Tn}, {W.cpad}] view with dense rows, got {tuple(out.shape)} / {out.stride()}")
+            ops.gemm_nt(h, W.head.w, out, Tn, W.cpad, D, batch=B, strideA=Tn * D, strideC=out.stride(0))
+            S.logits = out
+            return S
         logits = _e((B * Tn, W.cpad), BF16, dev)
         ops.gemm_nt(h, W.head.w, logits, B * Tn, W.cpad, D)
         S.logits = logits

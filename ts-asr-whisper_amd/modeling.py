@@ -331,6 +331,7 @@ class DiCoWEncoder(nn.Module):
         self._ctc_sig = None
 
     _CTC_PREFIXES = ("additional_layer.", "additional_self_attention_layer.", "subsample_conv", "lm_head.")
+    main_input_name = "input_features"       # read by the HF Trainer subclass of CTC pre-training (src/utils/trainers.py:52)
 
     def get_loss(self, logits, labels):
         """CTC loss of ``forward(..., return_logits=True).logits`` (reference encoder.py:108-135)."""
@@ -379,7 +380,11 @@ class DiCoWEncoder(nn.Module):
                 return_dict=None, stno_mask=None, return_logits=False, enrollments=None):
         _require_cuda(input_features, "DiCoWEncoder")
         if stno_mask is None:
-            raise ValueError("stno_mask is required")
+            # CTC pre-training (configs/pretrain: use_fddt false, a collator without STNO masks): no kernel reads the masks then;
+            # the engine still takes a tensor, so it gets zeros -- the result is bit-equal to a call with any valid mask
+            if self.config.use_fddt or enrollments is not None:
+                raise ValueError("stno_mask is required")
+            stno_mask = torch.zeros(input_features.shape[0], 4, self.config.max_source_positions, dtype=F32, device=input_features.device)
         _refuse_unsupported("DiCoWEncoder.forward", head_mask=head_mask, output_attentions=output_attentions or None,
                             output_hidden_states=output_hidden_states or None)
         ctc_ids = {id(p) for p in self.ctc_parameters()} if self.ctc_weight > 0.0 else set()
@@ -395,6 +400,45 @@ class DiCoWEncoder(nn.Module):
         if return_dict is False:
             return (out,)
         return ModelOutput(last_hidden_state=out, hidden_states=None, attentions=None)
+
+    def ctc_logits_into(self, input_features, stno_mask, out):
+        """Inference only: the logits of ``forward(..., return_logits=True)`` written into ``out``, a bf16 [B, Tn, cpad] view (unit
+        last stride, row stride cpad = vocab_size + 1 rounded up to 128, any batch stride) of a buffer the caller owns -- the windows
+        of ``ctc_decoding.chunked_ctc_logits`` land side by side without a concatenation."""
+        if torch.is_grad_enabled():
+            raise L.DicowError("ctc_logits_into keeps nothing for a backward pass: call it under torch.no_grad()")
+        if self.ctc_weight <= 0.0:
+            raise L.DicowError("ctc_logits_into needs the CTC head (ctc_weight > 0)")
+        enc_out = self.forward(input_features, stno_mask=stno_mask).last_hidden_state
+        enc_bf, enc_f, B, T = _ctc_head_input(enc_out)
+        self._ctc_engine().encode_logits(enc_bf, B, T, enc_f, out=out)
+        return out
+
+    def ctc_logits_layout(self):
+        """(Tn, cpad): CTC frames per encoder window and the padded row width of the logits the CTC head writes."""
+        if self.ctc_weight <= 0.0:
+            raise L.DicowError("ctc_logits_layout needs the CTC head (ctc_weight > 0)")
+        eng = self._ctc_engine()
+        return eng.frames(self.config.max_source_positions), eng.W.cpad
+
+
+def freeze_for_ctc_pretraining(encoder):
+    """Stage 0 of the reference's recipe (src/pretrain_encoder.py:42-51): only the CTC head trains -- ``additional_layer``,
+    ``additional_self_attention_layer``, ``subsample_conv1/2``, ``lm_head``, i.e. ``encoder.ctc_parameters()``.  With every other
+    parameter frozen the encoder proper runs its inference form (no activation is kept, see ``DiCoWEncoder.forward``)."""
+    head = {id(p) for p in encoder.ctc_parameters()}
+    if not head:
+        raise L.DicowError("freeze_for_ctc_pretraining: the encoder has no CTC head (ctc_weight > 0)")
+    for p in encoder.parameters():
+        p.requires_grad_(id(p) in head)
+    return encoder
+
+
+def _ctc_head_input(enc_out):
+    """Encoder output [B, T, D] -> (bf16 rows, the fp32 rows they were rounded from, B, T): what every entry into the CTC head feeds it."""
+    B, T, D = enc_out.shape
+    enc_f = enc_out.contiguous().to(F32).view(B * T, D)
+    return ops.cast_bf16(enc_f).view(B * T, D), enc_f, B, T
 
 
 class _CtcFn(torch.autograd.Function):
@@ -428,9 +472,7 @@ class _CtcLogitsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, enc, enc_out, *params):
         eng = enc._ctc_engine()
-        B, T, D = enc_out.shape
-        enc_f = enc_out.contiguous().to(F32).view(B * T, D)
-        enc_bf = ops.cast_bf16(enc_f).view(B * T, D)
+        enc_bf, enc_f, B, T = _ctc_head_input(enc_out)
         S = eng.encode_logits(enc_bf, B, T, enc_f)
         ctx.enc, ctx.S, ctx.params = enc, S, params
         return S.logits.view(B, S.Tn, -1)[:, :, :enc.config.vocab_size + 1]
@@ -462,8 +504,8 @@ class _CtcLossFn(torch.autograd.Function):
     def forward(ctx, enc, logits, labels):
         B, Tn, V1 = logits.shape
         dev = logits.device
-        if logits.dtype == BF16 and logits.stride(2) == 1 and logits.stride(0) == Tn * logits.stride(1):
-            buf, ld = logits, logits.stride(1)                # the padded rows produced by _CtcLogitsFn
+        if logits.dtype == BF16 and logits.stride(2) == 1 and logits.stride(0) == Tn * logits.stride(1) and logits.stride(1) % 2 == 0:
+            buf, ld = logits, logits.stride(1)                # the padded rows produced by _CtcLogitsFn (the kernels read bf16 pairs: even rows)
         else:
             ld = (V1 + 127) // 128 * 128
             buf = torch.zeros(B, Tn, ld, dtype=BF16, device=dev)
