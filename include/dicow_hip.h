@@ -437,6 +437,29 @@ int64_t dicow_logmel_ws_bytes(int B, int n_samples);
 int dicow_logmel(const float* wave, int B, int n_samples, const float* tw_cos, const float* tw_sin, const float* fb,
                  const int* mel_range, int M, float* out, void* ws, int64_t ws_bytes, void* stream);
 
+/* Background-noise mixing on the waveform, ahead of dicow_logmel (ABI 7, additive): RandomBackgroundNoise.__call__ of the reference
+ * (src/data/augmentations.py:395-429, the recipe's musan_augment_prob, gated per sample at src/data/local_datasets.py:205-206).  The draws
+ * (which rows, which clip, offset, SNR) are made on the host in the reference's order (ts-asr-whisper_amd/wave_augment.py) and arrive as a plan:
+ *   plan_i int32 [n_plan][4] = (row, clip, offset, len), plan_snr fp32 [n_plan] = float(10 ** (snr_db / 10)); rows distinct, len >= 1.
+ *   bank fp32: the peak-normalised mono clips back to back; clip k is bank[clip_start[k] .. clip_start[k] + clip_len[k]) (int64 / int32 tables).
+ * For every entry, with a = wave + row * ld_wave, o = out + row * ld_out, all arithmetic fp32:
+ *     n[i]  = bank[clip_start[clip] + offset + i] while offset + i < clip_len[clip], else 0                          i < len
+ *     scale = ||a[0:len)|| / (plan_snr * ||n||)     (the product first, as the reference); scale = 0 when ||n|| == 0, where the reference
+ *                                                   divides by zero and returns NaN: a silent crop gives a / 2
+ *     o[i]  = fma(scale, n[i], a[i]) * 0.5f                                                                          i < len
+ * Nothing else is written: rows that are not in the plan and samples at or behind len are the caller's (copy them first when out != wave).
+ * wave and out: 16-byte aligned, ld_wave and ld_out multiples of 4; out == wave (in place, ld_out == ld_wave) is legal, any other overlap
+ * of the two is not (unchecked: the rows are device data).  The crop may start at any element of the bank; nothing outside the clip is read.
+ * The two sums of squares are accumulated in fp64 per range of a row -- DICOW_NOISE_MIX_CHUNK samples up to 64 chunks, a larger multiple of
+ * it for longer rows, from the row's own len only -- stored in fixed workspace slots and added in ascending order by a fixed tree: no
+ * atomics, no host read, two launches, capturable into a graph, and a row's result depends on that row's inputs alone (bit-identical
+ * alone or beside other rows, and from run to run).  ws: dicow_noise_mix_ws_bytes(n_plan, longest len) bytes, 8-byte aligned, any contents;
+ * one call in flight per workspace.  n_plan == 0 launches nothing; n_plan <= 65535. */
+#define DICOW_NOISE_MIX_CHUNK 8192
+int64_t dicow_noise_mix_ws_bytes(int n_plan, int max_len);
+int dicow_noise_mix(const float* wave, int64_t ld_wave, float* out, int64_t ld_out, const float* bank, const int64_t* clip_start,
+                    const int* clip_len, const int* plan_i, const float* plan_snr, int n_plan, void* ws, int64_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ batch augmentation
  * The collator's training-time augmentations (reference src/data/collators.py:189-214), applied to the batch where it
  * already lives (HBM).  The random decisions are drawn on the host from the torch CPU generator in the reference's

@@ -13,8 +13,10 @@ from .modeling import (FDDT, DiCoWEncoder, DiCoW, DiCoWForConditionalGeneration,
                        shift_tokens_right, build_ts_tables, LoRALinear, add_decoder_lora, merge_lora, save_adapter, load_adapter,
                        freeze_for_ctc_pretraining)
 from .ctc_decoding import ctc_greedy_decode, chunked_ctc_logits  # noqa: F401
+from .wave_augment import NoiseBank, plan_background_noise, mix_background_noise, WaveFrontEnd  # noqa: F401
 from .optim import DiCoWAdamW, clip_grad_norm_, dicow_optimizer  # noqa: F401
 
 __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalGeneration", "SpeakerCommunicationBlock",
            "LoRALinear", "add_decoder_lora", "merge_lora", "save_adapter", "load_adapter", "DiCoWAdamW", "clip_grad_norm_", "dicow_optimizer",
-           "ctc_greedy_decode", "chunked_ctc_logits", "freeze_for_ctc_pretraining"]
+           "ctc_greedy_decode", "chunked_ctc_logits", "freeze_for_ctc_pretraining", "NoiseBank", "plan_background_noise", "mix_background_noise",
+           "WaveFrontEnd"]

@@ -69,6 +69,8 @@ class AttnDecodeArgs(C.Structure):
 
 ATTN_DECODE_MAX_GROUP = 8
 
+NOISE_MIX_CHUNK = 8192          # DICOW_NOISE_MIX_CHUNK: samples per partial sum of dicow_noise_mix (rows up to 64 chunks)
+
 LORA_MAX_R, LORA_MAX_SEG = 192, 24
 LORA_BLOCK, LORA_OUT_F32, LORA_GELU, LORA_MUL_AUX = 1, 2, 4, 8
 
@@ -183,6 +185,7 @@ _SIGS = {
     "dicow_whisper_timestamp_rules": [c_vp, c_i64, c_i, c_i, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
     "dicow_repetition_rules": [c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_i, c_f, c_i, c_vp],
     "dicow_ctc_greedy_decode": [c_vp, c_i, c_i64, c_i64, c_i, c_i, c_i, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp],
+    "dicow_noise_mix": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i64, c_vp],
     "dicow_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
     "dicow_fabric_emulate": [c_vp, c_i64, c_d, c_i, c_i, c_vp],
     "dicow_adamw_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_i, c_vp, c_f, c_vp],
@@ -261,6 +264,7 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
     "dicow_ctc_ws_bytes": [c_i, c_i, c_i],
     "dicow_multi_sumsq_ws_bytes": [c_i64],
     "dicow_lora_wgrad_ws_bytes": [c_i, c_i, c_i, c_i, c_i],
+    "dicow_noise_mix_ws_bytes": [c_i, c_i],
 }
 
 

@@ -559,7 +559,7 @@ class TrainStep:
     def __init__(self, model, lr=2e-6, fddt_lr_multiplier=100.0, weight_decay=0.0, max_grad_norm=1.0, warmup_steps=0,
                  max_steps=0, frozen_keywords=("decoder",), preheat_prefixes=None,
                  process_group=None, augmenter=None, use_fddt_only_n_steps=0, graph=False, use_fddt_only_n_epochs=0,
-                 steps_per_epoch=None, replica_sync="broadcast", split_streams=False):
+                 steps_per_epoch=None, replica_sync="broadcast", split_streams=False, front_end=None):
         self.model = model
         # split_streams=True: a batch of even size B >= 2 runs as two half batches on two HIP streams (same loss and gradients: the
         # halves' losses are weighted by their label counts, their gradients add in a fixed order -- SplitSync).  The HBM-bound row
@@ -592,6 +592,7 @@ class TrainStep:
         self._graph_pool = None
         self._eager_done = set()
         self.augmenter = augmenter          # augment.BatchAugmenter: the collator's training-time block, on the GPU
+        self.front_end = front_end          # wave_augment.WaveFrontEnd: batches that carry input_waves get noise + log-mel on the GPU first
         freeze_by_keyword(model, frozen_keywords)
         self.store = FlatStore(model, preheat_prefixes)
         self.opt = FusedAdamW(self.store, lr, fddt_lr_multiplier, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
@@ -675,6 +676,8 @@ class TrainStep:
     def _micro(self, batch, scale):
         if self.split_streams and self._can_split(batch):
             return self._micro_split(batch, scale)
+        if self.front_end is not None and "input_waves" in batch:      # the dataset's share (local_datasets.py:205-214), before the collator's
+            batch = self.front_end(dict(batch))
         if self.augmenter is not None:      # enrollments are collated "nested" and stay clean (collators.py:189,216-220)
             batch = self.augmenter(dict(batch))
         with tracing.range("forward"):
@@ -687,7 +690,7 @@ class TrainStep:
     def _can_split(self, batch):
         cfg = self.model.config
         lab = batch.get("labels")
-        return (self.split_streams and self.augmenter is None and cfg.ctc_weight == 0.0 and batch.get("enrollments") is None and
+        return (self.split_streams and self.augmenter is None and self.front_end is None and cfg.ctc_weight == 0.0 and batch.get("enrollments") is None and
                 lab is not None and lab.is_cuda and lab.shape[0] >= 2 and lab.shape[0] % 2 == 0 and
                 all(not torch.is_tensor(v) or v.dim() == 0 or v.shape[0] == lab.shape[0] for v in batch.values()))
 
@@ -768,7 +771,7 @@ class TrainStep:
     def _graph_step(self, batch):
         if self.reducer.world > 1 or self.reducer.force:
             raise NotImplementedError("TrainStep(graph=True) captures the single-GPU step; the bucketed side-stream exchange is not captured")
-        if self.model.config.ctc_weight > 0.0 or self.augmenter is not None:
+        if self.model.config.ctc_weight > 0.0 or self.augmenter is not None or self.front_end is not None:
             raise NotImplementedError("TrainStep(graph=True): the CTC label preparation / the augmentation planner read device data on "
                                       "the host; their steps cannot be captured")
         if self.warmup_phase and self.global_step >= self.use_fddt_only_n_steps:
