@@ -460,6 +460,47 @@ int64_t dicow_noise_mix_ws_bytes(int n_plan, int max_len);
 int dicow_noise_mix(const float* wave, int64_t ld_wave, float* out, int64_t ld_out, const float* bank, const int64_t* clip_start,
                     const int* clip_len, const int* plan_i, const float* plan_snr, int n_plan, void* ws, int64_t ws_bytes, void* stream);
 
+/* Diarization front end (ABI 7, additive): a diarization -- (speaker, start, end) segments -- to the STNO masks and the self-enrollment
+ * windows of SE-DiCoW, without a per-sample mask anywhere (reference src/data/local_datasets.py: get_stno_mask :162-182,
+ * _create_stno_masks :184-194, sample_enrollment_window / downsample_mean / select_random_internal_enrollment :216-292).
+ * The diarization arrives as a table the host builds in one sweep over the interval endpoints (ts-asr-whisper_amd/diar_front_end.py):
+ *   bounds int64 [E + 1], strictly increasing, 0 <= bounds[0], bounds[E] <= n_samples;
+ *   active uint64 [E]: bit s set when speaker s (0 <= s < S <= 64) is active on the samples [bounds[e], bounds[e + 1]).
+ * `bounds`, `active` and `targets` are HOST pointers: every entry point checks them before anything is launched (and returns -1 with
+ * dicow_last_error() set when they are bad) and then copies them into its workspace with the stream; everything else is device memory.
+ * Frames are DICOW_DIAR_FRAME samples (one encoder frame), bins DICOW_DIAR_BIN samples (0.1 s = 5 frames), windows DICOW_DIAR_WINDOW bins
+ * (30 s); T_total = ceil(n_samples / 480000) * 1500.  All three: integer arithmetic or correctly rounded fp32 in a fixed order, one writer
+ * per output element, no atomics, nothing allocated, bit-identical from run to run and whatever else is asked for in the same call.
+ *
+ * dicow_diar_frame_counts: for s < S and t < T_total, cnt[s * T_total + t] = samples of frame t on which s is active and excl[...] =
+ *   samples on which s is the only active speaker (frames behind the audio count 0).  One thread per (s, t): a binary search in bounds,
+ *   then a walk over the table entries that cut the frame.  E == 0 is legal (bounds holds one element).  ws: dicow_diar_table_ws_bytes(E).
+ * dicow_stno_from_counts: for target k (targets[k] = a speaker index, or -1 for the reference's unknown speaker, whose activity row is zero)
+ *   and frame t, with m_s = __fdiv_rn((float)cnt[s][t], 320.0f) and every product / difference rounded on its own (no contraction):
+ *     sil = prod_s (1 - m_s), s ascending;  else = the same product without the target;  tgt = m_t * else;
+ *     non = (1 - m_t) * (1 - else);  ovl = m_t - tgt          out[(k * 4 + c) * ld_out + t], c = 0..3 = S, T, N, O;  ld_out >= T_total
+ *   -- the bits numpy gives the reference.  Nothing outside [0, T_total) of a row is written.  ws: dicow_diar_targets_ws_bytes(n_targets).
+ * dicow_enrollment_windows: per target k (a speaker index; -1 has no enrollment and is refused), with nb = n_samples / 1600 full bins and
+ *   bin b = the sum of excl over the frames 5 b .. 5 b + 4:   w[i] = sum of the bins i .. i + 299, i < nw = nb - 299;  start[k] = the FIRST i
+ *   with maximal w, count[k] = that w, fallback[k] = 0.  When the maximum is 0 (the target is never alone) the same from cnt, fallback[k] = 1.
+ *   nb < 300 (under 30 s): nw = 1, w[0] = the sum of all bins.  weights (may be NULL): w[0 .. nw) of the pass that was taken, int32, row k at
+ *   weights + k * ld_w, ld_w >= nw.  One workgroup per target: chunked int64 prefix scan with carry into the workspace, window differences,
+ *   first-maximum reduction.  ws: dicow_enrollment_windows_ws_bytes(n_samples, n_targets). */
+#define DICOW_DIAR_FRAME 320
+#define DICOW_DIAR_BIN 1600
+#define DICOW_DIAR_WINDOW 300
+#define DICOW_DIAR_MAX_SPEAKERS 64
+int64_t dicow_diar_table_ws_bytes(int E);
+int64_t dicow_diar_targets_ws_bytes(int n_targets);
+int64_t dicow_enrollment_windows_ws_bytes(int64_t n_samples, int n_targets);
+int dicow_diar_frame_counts(const int64_t* bounds, const uint64_t* active, int E, int S, int64_t n_samples, int32_t* cnt, int32_t* excl,
+                            void* ws, int64_t ws_bytes, void* stream);
+int dicow_stno_from_counts(const int32_t* cnt, int S, int64_t n_samples, const int* targets, int n_targets, float* out, int64_t ld_out,
+                           void* ws, int64_t ws_bytes, void* stream);
+int dicow_enrollment_windows(const int32_t* cnt, const int32_t* excl, int S, int64_t n_samples, const int* targets, int n_targets,
+                             int32_t* start, int32_t* count, int32_t* fallback, int32_t* weights, int64_t ld_w, void* ws, int64_t ws_bytes,
+                             void* stream);
+
 /* ------------------------------------------------------------------------------------------------ batch augmentation
  * The collator's training-time augmentations (reference src/data/collators.py:189-214), applied to the batch where it
  * already lives (HBM).  The random decisions are drawn on the host from the torch CPU generator in the reference's

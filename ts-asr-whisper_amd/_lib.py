@@ -71,6 +71,8 @@ ATTN_DECODE_MAX_GROUP = 8
 
 NOISE_MIX_CHUNK = 8192          # DICOW_NOISE_MIX_CHUNK: samples per partial sum of dicow_noise_mix (rows up to 64 chunks)
 
+DIAR_FRAME, DIAR_BIN, DIAR_WINDOW, DIAR_MAX_SPEAKERS = 320, 1600, 300, 64   # DICOW_DIAR_*: samples per frame / bin, bins per window
+
 LORA_MAX_R, LORA_MAX_SEG = 192, 24
 LORA_BLOCK, LORA_OUT_F32, LORA_GELU, LORA_MUL_AUX = 1, 2, 4, 8
 
@@ -186,6 +188,9 @@ _SIGS = {
     "dicow_repetition_rules": [c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_i, c_f, c_i, c_vp],
     "dicow_ctc_greedy_decode": [c_vp, c_i, c_i64, c_i64, c_i, c_i, c_i, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp],
     "dicow_noise_mix": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i64, c_vp],
+    "dicow_diar_frame_counts": [c_vp, c_vp, c_i, c_i, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "dicow_stno_from_counts": [c_vp, c_i, c_i64, c_vp, c_i, c_vp, c_i64, c_vp, c_i64, c_vp],
+    "dicow_enrollment_windows": [c_vp, c_vp, c_i, c_i64, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
     "dicow_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
     "dicow_fabric_emulate": [c_vp, c_i64, c_d, c_i, c_i, c_vp],
     "dicow_adamw_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_i, c_vp, c_f, c_vp],
@@ -265,6 +270,9 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
     "dicow_multi_sumsq_ws_bytes": [c_i64],
     "dicow_lora_wgrad_ws_bytes": [c_i, c_i, c_i, c_i, c_i],
     "dicow_noise_mix_ws_bytes": [c_i, c_i],
+    "dicow_diar_table_ws_bytes": [c_i],
+    "dicow_diar_targets_ws_bytes": [c_i],
+    "dicow_enrollment_windows_ws_bytes": [c_i64, c_i],
 }
 
 

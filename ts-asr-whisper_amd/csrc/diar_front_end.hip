@@ -1,0 +1,268 @@
+// Diarization front end: (speaker, start, end) segments -> per-frame sample counts -> STNO masks and self-enrollment windows, for
+// recordings whose features already live in HBM (reference src/data/local_datasets.py: get_stno_mask :162-182, _create_stno_masks :184-194,
+// downsample_mean / sample_enrollment_window / select_random_internal_enrollment :216-292).  The reference rasterises a [S, n_samples] mask
+// per target speaker and pools it; here the diarization is a table of E + 1 interval endpoints and E speaker bitmasks (built on the host in
+// one sweep, ts-asr-whisper_amd/diar_front_end.py), and no per-sample array exists anywhere.
+//
+//   1. diar_frame_counts_kernel   thread (s, t): binary search for the table entry that holds the frame's first sample, then a walk over
+//                                 the entries that cut the frame: cnt = samples with bit s set, excl = samples whose mask is exactly bit s.
+//   2. stno_from_counts_kernel    thread (k, t): m_s = cnt / 320 (correctly rounded), the reference's products in its order, every operation
+//                                 rounded on its own: contraction is switched off for this file, because hipcc's default turns m - m * e
+//                                 and (1 - m)(...) into fmas and changes last bits against numpy (HIP's __fmul_rn / __fsub_rn are plain
+//                                 operators and get contracted like any other).
+//   3. enrollment_windows_kernel  one workgroup per target: bins of 5 frames, int64 prefix sums P[0 .. nb] into the workspace chunk by chunk
+//                                 with a running carry, w[i] = P[i + 300] - P[i], then the FIRST index of the maximum (ties are the rule:
+//                                 any stretch of more than 30 s of solo speech is a plateau).  All zero -> once more from cnt (the
+//                                 reference's fallback for a speaker who is never alone).
+// Integer arithmetic throughout 1 and 3; every output element has exactly one writer; no atomics; bit-reproducible.
+// The tables are HOST arrays: validated before anything is launched, then copied into the workspace with the stream.
+#include "common.h"
+
+#pragma clang fp contract(off)                // every fp32 operation below rounds on its own, as numpy's do
+
+#define DFE_BLOCK 256
+#define DFE_ITEMS 4                           // bins per thread and chunk of the scan
+#define DFE_CHUNK (DFE_BLOCK * DFE_ITEMS)
+#define DFE_FRAMES_PER_BIN (DICOW_DIAR_BIN / DICOW_DIAR_FRAME)
+#define DFE_WINDOW_SAMPLES 480000             // 30 s
+#define DFE_WINDOW_FRAMES 1500
+
+static inline int64_t dfe_t_total(int64_t n_samples) { return (n_samples + DFE_WINDOW_SAMPLES - 1) / DFE_WINDOW_SAMPLES * DFE_WINDOW_FRAMES; }
+
+__global__ void __launch_bounds__(DFE_BLOCK) diar_frame_counts_kernel(const int64_t* __restrict__ bounds, const uint64_t* __restrict__ active,
+                                                                      int E, int T_total, int* __restrict__ cnt, int* __restrict__ excl) {
+    const int t = blockIdx.x * DFE_BLOCK + threadIdx.x, s = blockIdx.y;
+    if (t >= T_total) return;
+    const int64_t f0 = (int64_t)t * DICOW_DIAR_FRAME, f1 = f0 + DICOW_DIAR_FRAME;
+    // e = the first entry that ends behind f0 (entries are [bounds[e], bounds[e + 1])): the smallest e in [0, E] with bounds[e + 1] > f0, E if none
+    int lo = 0, hi = E;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (bounds[mid + 1] > f0) hi = mid; else lo = mid + 1;
+    }
+    const uint64_t bit = (uint64_t)1 << s;
+    int c = 0, x = 0;
+    for (int e = lo; e < E; ++e) {
+        const int64_t b0 = bounds[e];
+        if (b0 >= f1) break;
+        const int64_t b1 = bounds[e + 1];
+        const int n = (int)(min(b1, f1) - max(b0, f0));          // >= 1: b1 > f0 by the search (and bounds increase), b0 < f1
+        const uint64_t a = active[e];
+        if (a & bit) c += n;
+        if (a == bit) x += n;
+    }
+    const int64_t o = (int64_t)s * T_total + t;
+    cnt[o] = c;
+    excl[o] = x;
+}
+
+__global__ void __launch_bounds__(DFE_BLOCK) stno_from_counts_kernel(const int* __restrict__ cnt, int S, int T_total, const int* __restrict__ targets,
+                                                                     float* __restrict__ out, int64_t ld_out) {
+    const int t = blockIdx.x * DFE_BLOCK + threadIdx.x, k = blockIdx.y;
+    if (t >= T_total) return;
+    const int tg = targets[k];
+    float sil = 1.0f, other = 1.0f, mt = 0.0f;                   // (target -1: the reference's appended zero row -- m_t = 0, and its factor 1 - 0
+    for (int s = 0; s < S; ++s) {                                //  multiplies sil by exactly 1)
+        const float m = (float)cnt[(int64_t)s * T_total + t] / (float)DICOW_DIAR_FRAME;      // IEEE division (hipcc's default for fp32)
+        const float q = 1.0f - m;
+        sil = sil * q;                                           // (1 * q == q: the same bits as numpy's reduction, which starts from row 0)
+        if (s == tg) mt = m; else other = other * q;
+    }
+    const float tgt = mt * other;
+    const float non = (1.0f - mt) * (1.0f - other);
+    const float ovl = mt - tgt;
+    float* o = out + (int64_t)k * 4 * ld_out + t;
+    o[0] = sil;
+    o[ld_out] = tgt;
+    o[2 * ld_out] = non;
+    o[3 * ld_out] = ovl;
+}
+
+// One workgroup per target.  P (int64 [nb + 1]) is this target's slice of the workspace; written and read by this workgroup only, with
+// __syncthreads() between (block-level visibility of global writes).
+__global__ void __launch_bounds__(DFE_BLOCK) enrollment_windows_kernel(const int* __restrict__ cnt, const int* __restrict__ excl, int T_total, int nb,
+                                                                       const int* __restrict__ targets, int64_t* ws_prefix,
+                                                                       int* __restrict__ start, int* __restrict__ count, int* __restrict__ fallback,
+                                                                       int* __restrict__ weights, int64_t ld_w) {
+    __shared__ int64_t scan[2][DFE_BLOCK];
+    __shared__ int best_w[DFE_BLOCK], best_i[DFE_BLOCK];
+    const int tid = threadIdx.x, k = blockIdx.x;
+    const int tg = targets[k];
+    int64_t* P = ws_prefix + (int64_t)k * ((int64_t)nb + 1);
+    const int nw = nb >= DICOW_DIAR_WINDOW ? nb - DICOW_DIAR_WINDOW + 1 : 1;
+    const int span = nb >= DICOW_DIAR_WINDOW ? DICOW_DIAR_WINDOW : nb;           // bins per window
+    int* wrow = weights ? weights + (int64_t)k * ld_w : nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        const int* src = (pass == 0 ? excl : cnt) + (int64_t)tg * T_total;
+        // ---- prefix sums over the bins, DFE_CHUNK at a time; `carry` (uniform) = the sum of everything before the chunk
+        int64_t carry = 0;
+        if (tid == 0) P[0] = 0;
+        for (int c0 = 0; c0 < nb; c0 += DFE_CHUNK) {
+            int v[DFE_ITEMS];
+            int64_t mine = 0;
+#pragma unroll
+            for (int j = 0; j < DFE_ITEMS; ++j) {
+                const int b = c0 + tid * DFE_ITEMS + j;
+                int sum = 0;
+                if (b < nb) {
+                    const int* f = src + (int64_t)b * DFE_FRAMES_PER_BIN;          // 5 b + 4 < 5 nb <= T_total
+#pragma unroll
+                    for (int q = 0; q < DFE_FRAMES_PER_BIN; ++q) sum += f[q];
+                }
+                v[j] = sum;
+                mine += sum;
+            }
+            // inclusive scan of the 256 thread sums (Hillis-Steele, two buffers)
+            int cur = 0;
+            scan[0][tid] = mine;
+            __syncthreads();
+#pragma unroll
+            for (int o = 1; o < DFE_BLOCK; o <<= 1) {
+                const int64_t a = scan[cur][tid] + (tid >= o ? scan[cur][tid - o] : 0);
+                scan[cur ^ 1][tid] = a;
+                cur ^= 1;
+                __syncthreads();
+            }
+            int64_t run = carry + scan[cur][tid] - mine;                           // exclusive
+            const int64_t total = scan[cur][DFE_BLOCK - 1];
+#pragma unroll
+            for (int j = 0; j < DFE_ITEMS; ++j) {
+                const int b = c0 + tid * DFE_ITEMS + j;
+                run += v[j];
+                if (b < nb) P[b + 1] = run;
+            }
+            carry += total;
+            __syncthreads();                                                       // scan[] is reused by the next chunk
+        }
+        __syncthreads();                                                           // P complete and visible to the workgroup
+        // ---- window sums and the first maximum
+        int bw = -1, bi = 0;
+        for (int i = tid; i < nw; i += DFE_BLOCK) {
+            const int w = (int)(P[i + span] - P[i]);                               // <= 300 * 1600
+            if (wrow) wrow[i] = w;                                                 // (a fallback pass overwrites the row: same thread, same slot)
+            if (w > bw) { bw = w; bi = i; }                                        // ascending i per thread: strict > keeps the first
+        }
+        best_w[tid] = bw;
+        best_i[tid] = bi;
+        __syncthreads();
+        for (int o = DFE_BLOCK / 2; o > 0; o >>= 1) {
+            if (tid < o) {
+                const int w2 = best_w[tid + o], i2 = best_i[tid + o];
+                if (w2 > best_w[tid] || (w2 == best_w[tid] && i2 < best_i[tid])) { best_w[tid] = w2; best_i[tid] = i2; }
+            }
+            __syncthreads();
+        }
+        const int w_max = best_w[0], i_max = best_i[0];
+        __syncthreads();                                                           // everyone has read the result before best_*[] is reused
+        if (w_max > 0 || pass == 1) {                                              // (uniform: every thread read the same LDS words)
+            if (tid == 0) { start[k] = i_max; count[k] = w_max; fallback[k] = pass; }
+            break;
+        }
+    }
+}
+
+extern "C" int64_t dicow_diar_table_ws_bytes(int E) {
+    if (E < 0) { dicow_set_error("diar_table_ws_bytes: negative E=%d", E); return -1; }
+    return ((int64_t)2 * E + 1) * 8;
+}
+
+extern "C" int64_t dicow_diar_targets_ws_bytes(int n_targets) {
+    if (n_targets < 0) { dicow_set_error("diar_targets_ws_bytes: negative n_targets=%d", n_targets); return -1; }
+    return ((int64_t)n_targets * 4 + 7) / 8 * 8;
+}
+
+extern "C" int64_t dicow_enrollment_windows_ws_bytes(int64_t n_samples, int n_targets) {
+    if (n_samples < 0 || n_targets < 0) {
+        dicow_set_error("enrollment_windows_ws_bytes: negative size n_samples=%lld n_targets=%d", (long long)n_samples, n_targets);
+        return -1;
+    }
+    return ((int64_t)n_targets * 4 + 7) / 8 * 8 + (int64_t)n_targets * (n_samples / DICOW_DIAR_BIN + 1) * 8;
+}
+
+// the checks the three entry points share
+static int dfe_check_sizes(const char* who, int S, int64_t n_samples) {
+    DICOW_REQUIRE(S >= 1 && S <= DICOW_DIAR_MAX_SPEAKERS, "%s: S=%d outside [1, %d]", who, S, DICOW_DIAR_MAX_SPEAKERS);
+    DICOW_REQUIRE(n_samples >= 0, "%s: negative n_samples=%lld", who, (long long)n_samples);
+    DICOW_REQUIRE(dfe_t_total(n_samples) <= 0x7fffffff, "%s: n_samples=%lld gives more than 2^31 - 1 frames", who, (long long)n_samples);
+    return DICOW_OK;
+}
+
+static int dfe_check_targets(const char* who, const int* targets, int n_targets, int lo, int S) {
+    DICOW_REQUIRE(n_targets >= 0 && n_targets <= 65535, "%s: n_targets=%d outside [0, 65535]", who, n_targets);
+    DICOW_REQUIRE(n_targets == 0 || targets, "%s: null targets", who);
+    for (int k = 0; k < n_targets; ++k)
+        DICOW_REQUIRE(targets[k] >= lo && targets[k] < S, "%s: targets[%d]=%d outside [%d, %d)", who, k, targets[k], lo, S);
+    return DICOW_OK;
+}
+
+#define DFE_HIP(call, who) do { hipError_t e_ = (call); if (e_ != hipSuccess) DICOW_FAIL(DICOW_ERR_LAUNCH, "%s: %s", who, hipGetErrorString(e_)); } while (0)
+
+extern "C" int dicow_diar_frame_counts(const int64_t* bounds, const uint64_t* active, int E, int S, int64_t n_samples, int32_t* cnt, int32_t* excl,
+                                       void* ws, int64_t ws_bytes, void* stream) {
+    DICOW_REQUIRE(E >= 0, "diar_frame_counts: negative E=%d", E);
+    if (int rc = dfe_check_sizes("diar_frame_counts", S, n_samples)) return rc;
+    DICOW_REQUIRE(bounds && (E == 0 || active) && cnt && excl && ws, "diar_frame_counts: null pointer");
+    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, "diar_frame_counts: ws not 8-byte aligned");
+    const int64_t need = ((int64_t)2 * E + 1) * 8;
+    DICOW_REQUIRE(ws_bytes >= need, "diar_frame_counts: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)need);
+    DICOW_REQUIRE(bounds[0] >= 0 && bounds[E] <= n_samples, "diar_frame_counts: bounds [%lld, %lld] outside [0, n_samples=%lld]",
+                  (long long)bounds[0], (long long)bounds[E], (long long)n_samples);
+    const uint64_t legal = S == 64 ? ~(uint64_t)0 : (((uint64_t)1 << S) - 1);
+    for (int e = 0; e < E; ++e) {
+        DICOW_REQUIRE(bounds[e] < bounds[e + 1], "diar_frame_counts: bounds not strictly increasing at %d (%lld, %lld)", e, (long long)bounds[e],
+                      (long long)bounds[e + 1]);
+        DICOW_REQUIRE((active[e] & ~legal) == 0, "diar_frame_counts: active[%d] names a speaker >= S=%d", e, S);
+    }
+    const int T_total = (int)dfe_t_total(n_samples);
+    if (T_total == 0) return DICOW_OK;
+    hipStream_t st = (hipStream_t)stream;
+    int64_t* d_bounds = (int64_t*)ws;
+    uint64_t* d_active = (uint64_t*)ws + (E + 1);
+    DFE_HIP(hipMemcpyAsync(d_bounds, bounds, ((int64_t)E + 1) * 8, hipMemcpyHostToDevice, st), "diar_frame_counts: table upload");
+    if (E > 0) DFE_HIP(hipMemcpyAsync(d_active, active, (int64_t)E * 8, hipMemcpyHostToDevice, st), "diar_frame_counts: table upload");
+    diar_frame_counts_kernel<<<dim3(dicow_cdiv(T_total, DFE_BLOCK), S), DFE_BLOCK, 0, st>>>(d_bounds, d_active, E, T_total, cnt, excl);
+    DICOW_CHECK_LAUNCH("diar_frame_counts_kernel");
+    return DICOW_OK;
+}
+
+extern "C" int dicow_stno_from_counts(const int32_t* cnt, int S, int64_t n_samples, const int* targets, int n_targets, float* out, int64_t ld_out,
+                                      void* ws, int64_t ws_bytes, void* stream) {
+    if (int rc = dfe_check_sizes("stno_from_counts", S, n_samples)) return rc;
+    if (int rc = dfe_check_targets("stno_from_counts", targets, n_targets, -1, S)) return rc;
+    const int T_total = (int)dfe_t_total(n_samples);
+    DICOW_REQUIRE(ld_out >= T_total, "stno_from_counts: ld_out=%lld shorter than T_total=%d", (long long)ld_out, T_total);
+    if (n_targets == 0 || T_total == 0) return DICOW_OK;
+    DICOW_REQUIRE(cnt && out && ws, "stno_from_counts: null pointer");
+    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, "stno_from_counts: ws not 8-byte aligned");
+    const int64_t need = ((int64_t)n_targets * 4 + 7) / 8 * 8;
+    DICOW_REQUIRE(ws_bytes >= need, "stno_from_counts: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    DFE_HIP(hipMemcpyAsync(ws, targets, (int64_t)n_targets * 4, hipMemcpyHostToDevice, st), "stno_from_counts: targets upload");
+    stno_from_counts_kernel<<<dim3(dicow_cdiv(T_total, DFE_BLOCK), n_targets), DFE_BLOCK, 0, st>>>(cnt, S, T_total, (const int*)ws, out, ld_out);
+    DICOW_CHECK_LAUNCH("stno_from_counts_kernel");
+    return DICOW_OK;
+}
+
+extern "C" int dicow_enrollment_windows(const int32_t* cnt, const int32_t* excl, int S, int64_t n_samples, const int* targets, int n_targets,
+                                        int32_t* start, int32_t* count, int32_t* fallback, int32_t* weights, int64_t ld_w, void* ws,
+                                        int64_t ws_bytes, void* stream) {
+    if (int rc = dfe_check_sizes("enrollment_windows", S, n_samples)) return rc;
+    if (int rc = dfe_check_targets("enrollment_windows", targets, n_targets, 0, S)) return rc;
+    const int64_t nb64 = n_samples / DICOW_DIAR_BIN;
+    DICOW_REQUIRE(nb64 <= 0x7ffffff0, "enrollment_windows: n_samples=%lld gives too many bins", (long long)n_samples);
+    const int nb = (int)nb64;
+    const int nw = nb >= DICOW_DIAR_WINDOW ? nb - DICOW_DIAR_WINDOW + 1 : 1;
+    DICOW_REQUIRE(!weights || ld_w >= nw, "enrollment_windows: ld_w=%lld shorter than the %d windows", (long long)ld_w, nw);
+    if (n_targets == 0) return DICOW_OK;
+    DICOW_REQUIRE(cnt && excl && start && count && fallback && ws, "enrollment_windows: null pointer");
+    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, "enrollment_windows: ws not 8-byte aligned");
+    const int64_t tbytes = ((int64_t)n_targets * 4 + 7) / 8 * 8;
+    const int64_t need = tbytes + (int64_t)n_targets * (nb64 + 1) * 8;
+    DICOW_REQUIRE(ws_bytes >= need, "enrollment_windows: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    DFE_HIP(hipMemcpyAsync(ws, targets, (int64_t)n_targets * 4, hipMemcpyHostToDevice, st), "enrollment_windows: targets upload");
+    enrollment_windows_kernel<<<n_targets, DFE_BLOCK, 0, st>>>(cnt, excl, (int)dfe_t_total(n_samples), nb, (const int*)ws,
+                                                               (int64_t*)((char*)ws + tbytes), start, count, fallback, weights, ld_w);
+    DICOW_CHECK_LAUNCH("enrollment_windows_kernel");
+    return DICOW_OK;
+}
