@@ -8,6 +8,7 @@
 //   ctc_lse_kernel        one workgroup per (b,t) row: log-sum-exp of the bf16 logits (streams V+1 values once)
 //   ctc_alpha_beta_kernel one workgroup per utterance: both recursions with the 2L+1 states spread over the threads,
 //                         state vectors ping-pong in LDS, log alpha / log beta kept in the caller's workspace
+//   ctc_sum_kernel        one workgroup: the step's loss, added up in utterance order (bit-reproducible)
 //   ctc_grad_kernel       one workgroup per (b,t) row: label posteriors accumulated in an LDS hash table (repeated
 //                         labels / the L+1 blanks collide by design), then one dense pass writes the bf16 gradient
 #include "common.h"
@@ -91,7 +92,6 @@ __global__ void __launch_bounds__(CTC_THREADS) ctc_alpha_beta_kernel(const dicow
         nll = tot <= CTC_NEG ? INFINITY : -tot;
         a.nll[b] = nll;
         a.tlen[b] = (float)tl;
-        if (isfinite(nll)) atomicAdd(a.loss_sum, nll / (float)(tl > 0 ? tl : 1));        // zero_infinity: inf -> 0
     }
     __syncthreads();
     // ---- beta (state vector shifted by 0, two guard cells on the right)
@@ -113,6 +113,27 @@ __global__ void __launch_bounds__(CTC_THREADS) ctc_alpha_beta_kernel(const dicow
         if (s < Smax) lb[(int64_t)t * Smax + s] = v;
         __syncthreads();
     }
+}
+
+// The step's CTC loss is sum_b nll_b / max(tl_b, 1) over the feasible utterances (zero_infinity: inf -> 0) IN UTTERANCE ORDER: a
+// one-workgroup launch that follows ctc_alpha_beta_kernel on the same stream, with a fixed assignment of utterances to threads and
+// a fixed tree, exactly as ce_sum_kernel (loss.hip) does for the decoder loss and for the same reason -- a float atomicAdd per
+// utterance made the last bits of the logged loss depend on the order the B workgroups retired in.
+#define CTC_SUM_THREADS 256
+__global__ void __launch_bounds__(CTC_SUM_THREADS) ctc_sum_kernel(const float* nll, const float* tlen, int B, float* loss_sum) {
+    __shared__ float tot[CTC_SUM_THREADS];
+    float t = 0.f;
+    for (int b = threadIdx.x; b < B; b += CTC_SUM_THREADS) {
+        const float n = nll[b];
+        if (isfinite(n)) t += n / fmaxf(tlen[b], 1.f);
+    }
+    tot[threadIdx.x] = t;
+    __syncthreads();
+    for (int o = CTC_SUM_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) tot[threadIdx.x] += tot[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss_sum[0] += tot[0];
 }
 
 #define HT 2048
@@ -188,6 +209,8 @@ extern "C" int dicow_ctc_loss_fwd(const dicow_ctc_args* a, void* stream) {
     DICOW_CHECK_LAUNCH("ctc_lse");
     hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3(a->B), dim3(CTC_THREADS), 0, (hipStream_t)stream, *a);
     DICOW_CHECK_LAUNCH("ctc_alpha_beta");
+    hipLaunchKernelGGL(ctc_sum_kernel, dim3(1), dim3(CTC_SUM_THREADS), 0, (hipStream_t)stream, a->nll, a->tlen, a->B, a->loss_sum);
+    DICOW_CHECK_LAUNCH("ctc_loss_fwd (ordered sum)");
     return DICOW_OK;
 }
 
