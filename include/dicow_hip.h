@@ -501,6 +501,29 @@ int dicow_enrollment_windows(const int32_t* cnt, const int32_t* excl, int S, int
                              int32_t* start, int32_t* count, int32_t* fallback, int32_t* weights, int64_t ld_w, void* ws, int64_t ws_bytes,
                              void* stream);
 
+/* External enrollment mixtures (ABI 7, additive): the audio of the reference's generate_enrollment_mixture (src/data/local_datasets.py:
+ * 355-436) -- a few utterances of an enrollment bank, shifted and summed into one 30 s input per row -- written where dicow_logmel reads
+ * it.  The draws are made on the host in the reference's order (ts-asr-whisper_amd/enrollment_mix.py) and arrive as a plan of tracks:
+ *   plan int32 [n_tracks][4] = (row, clip, off, len): samples [0, len) of clip `clip` land on samples [off, off + len) of row `row`;
+ *   rows non-decreasing (the tracks of a row are consecutive, and their order is the order of the sum), at most
+ *   DICOW_ENR_MIX_MAX_TRACKS tracks per row; a row may have none.
+ *   bank fp32: the clips back to back, clip k at bank[clip_start[k] .. clip_start[k] + clip_len[k]); clips may start at any element.
+ * For every row r < B and sample t < n, with x_k = bank[clip_start[clip_k] + t - off_k] over the row's tracks k, in plan order, that
+ * cover t:      out[r * ld_out + t] = ((x_0 + x_1) + x_2) + ...   one __fadd_rn per further track; the bits of x_0 when one track covers t;
+ *                                     exactly 0 when none does (so the call also pads the row to n samples).
+ * Every sample of every row is written by exactly one thread, whatever was there before: no atomics, no workspace, no host read, nothing
+ * allocated, one launch, capturable into a graph, and the result does not depend on the launch geometry (bit-identical from run to run,
+ * and for a row alone or beside other rows).  16-byte loads are used only where all four samples of a vector lie inside a track, single
+ * loads at its edges: nothing outside a clip is read, nothing outside [0, n) of a row is written.
+ * out: 16-byte aligned, ld_out a multiple of 4 and >= n.  The plan is passed twice: plan_host (and clip_len_host, the n_clips clip
+ * lengths) are HOST arrays that are checked before anything is launched -- row in [0, B), rows non-decreasing, clip in [0, n_clips),
+ * off >= 0, 1 <= len <= clip_len, off + len <= n, the track cap; a failure returns -1 with dicow_last_error() set -- and plan_dev is the
+ * same table in device memory, which is what the kernel reads (a captured graph replays on whatever plan_dev then holds: the caller
+ * answers for a table it writes there later).  B <= 65535; n_tracks == 0 writes zeros. */
+#define DICOW_ENR_MIX_MAX_TRACKS 8
+int dicow_enrollment_mix(float* out, int64_t ld_out, int B, int n, const float* bank, const int64_t* clip_start, const int32_t* plan_dev,
+                         const int32_t* plan_host, int n_tracks, const int32_t* clip_len_host, int n_clips, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ batch augmentation
  * The collator's training-time augmentations (reference src/data/collators.py:189-214), applied to the batch where it
  * already lives (HBM).  The random decisions are drawn on the host from the torch CPU generator in the reference's

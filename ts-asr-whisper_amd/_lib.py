@@ -73,6 +73,8 @@ NOISE_MIX_CHUNK = 8192          # DICOW_NOISE_MIX_CHUNK: samples per partial sum
 
 DIAR_FRAME, DIAR_BIN, DIAR_WINDOW, DIAR_MAX_SPEAKERS = 320, 1600, 300, 64   # DICOW_DIAR_*: samples per frame / bin, bins per window
 
+ENR_MIX_MAX_TRACKS = 8          # DICOW_ENR_MIX_MAX_TRACKS: tracks per row of dicow_enrollment_mix
+
 LORA_MAX_R, LORA_MAX_SEG = 192, 24
 LORA_BLOCK, LORA_OUT_F32, LORA_GELU, LORA_MUL_AUX = 1, 2, 4, 8
 
@@ -191,6 +193,7 @@ _SIGS = {
     "dicow_diar_frame_counts": [c_vp, c_vp, c_i, c_i, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp],
     "dicow_stno_from_counts": [c_vp, c_i, c_i64, c_vp, c_i, c_vp, c_i64, c_vp, c_i64, c_vp],
     "dicow_enrollment_windows": [c_vp, c_vp, c_i, c_i64, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
+    "dicow_enrollment_mix": [c_vp, c_i64, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_vp],
     "dicow_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
     "dicow_fabric_emulate": [c_vp, c_i64, c_d, c_i, c_i, c_vp],
     "dicow_adamw_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_i, c_vp, c_f, c_vp],

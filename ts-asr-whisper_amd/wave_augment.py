@@ -47,6 +47,20 @@ def _prepare_clip(noise: torch.Tensor) -> torch.Tensor:
     return (noise / peak)[0]
 
 
+def read_pcm16(path, sample_rate: int = 16000, who: str = "NoiseBank") -> torch.Tensor:
+    """A 16-bit PCM WAV file -> fp32 ``[C, n]``, read with the standard library and scaled by 1 / 32768 as ``torchaudio.load`` normalises.
+    Another sample width or another rate is refused (no resampling here)."""
+    with _wave.open(str(path), "rb") as w:
+        if w.getsampwidth() != 2:
+            raise ValueError(f"{who}: {path} has {8 * w.getsampwidth()}-bit samples; only 16-bit PCM is read")
+        if w.getframerate() != sample_rate:
+            raise ValueError(f"{who}: {path} is sampled at {w.getframerate()} Hz, not {sample_rate} Hz; resample the files "
+                             "first (this loader does not resample)")
+        ch = w.getnchannels()
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2")
+    return torch.from_numpy(pcm.astype(np.float32) / 32768.0).reshape(-1, ch).t().contiguous()
+
+
 class NoiseBank:
     """The noise clips of the reference's ``noise_files_list``, prepared once and kept on the device: one flat fp32 buffer ``data`` with
     clip k at ``data[clip_start[k] : clip_start[k] + clip_len[k]]`` (``clip_start`` int64 [n], ``clip_len`` int32 [n], both on the device;
@@ -94,18 +108,7 @@ class NoiseBank:
         files = list(pathlib.Path(noise_dir).glob('**/*.wav'))
         if len(files) == 0:
             raise IOError(f'No .wav file found in the noise directory `{noise_dir}`')
-        clips = []
-        for f in files:
-            with _wave.open(str(f), "rb") as w:
-                if w.getsampwidth() != 2:
-                    raise ValueError(f"NoiseBank: {f} has {8 * w.getsampwidth()}-bit samples; only 16-bit PCM is read")
-                if w.getframerate() != sample_rate:
-                    raise ValueError(f"NoiseBank: {f} is sampled at {w.getframerate()} Hz, not {sample_rate} Hz; resample the noise set "
-                                     "first (this loader does not resample)")
-                ch = w.getnchannels()
-                pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2")
-            clips.append(torch.from_numpy(pcm.astype(np.float32) / 32768.0).reshape(-1, ch).t().contiguous())
-        bank = cls.from_tensors(clips, device)
+        bank = cls.from_tensors([read_pcm16(f, sample_rate, "NoiseBank") for f in files], device)
         bank.files = files
         return bank
 
