@@ -253,6 +253,9 @@ typedef struct {
                                                        Same softmax, same lse (natural log) -- the kernel saves a multiply-add per score */
 } dicow_attn_fwd_args;
 int dicow_attn_fwd(const dicow_attn_fwd_args* a, void* stream);
+/* Which kernel body dicow_attn_fwd would run (host logic, no launch): "occ4_spec" (q_log2: base-2 scores, speculative first pass) or
+ * "occ4"; NULL where the call would return DICOW_ERR_INVALID, or for a NULL argument. */
+const char* dicow_attn_fwd_route(const dicow_attn_fwd_args* a);
 
 /* The decoder step's attention (ONE query row per decoder row) with the K/V row chosen per query row: softmax(q K^T) V, head_dim 64,
  * scaling 1.0 (q pre-scaled), bf16 in and out, fp32 inside, fixed summation order (two launches give the same bits).  Same
@@ -361,6 +364,12 @@ typedef struct {
 int dicow_attn_bwd(const dicow_attn_bwd_args* a, void* stream);
 int64_t dicow_attn_bwd_colsum_ws_bytes(int B, int H, int Lq, int Lk);
 int64_t dicow_attn_bwd_fused_ws_bytes(int B, int H, int Lq, int Lk);
+/* Which form dicow_attn_bwd would run (host logic, no launch): "fused" or "dq_dkv" (the two-kernel form); NULL where the call would
+ * return DICOW_ERR_INVALID, or for a NULL argument. */
+const char* dicow_attn_bwd_route(const dicow_attn_bwd_args* a);
+/* The shape half of the fused rule -- everything except "fused_ws was passed and is large enough": 1 where a workspace of
+ * dicow_attn_bwd_fused_ws_bytes() would make the call run fused (callers allocate it only then), else 0. */
+int dicow_attn_bwd_fused_eligible(int B, int H, int Lq, int Lk, int causal, int fused_mode);
 /* error bits the last fused launch left in its workspace (synchronise the stream first): 0 = fine, 1 = a hand-off wait timed
    out, 2 = a (batch, head) was spread over several XCDs; -1 = the copy failed.  dq is not to be trusted when non-zero. */
 int dicow_attn_bwd_fused_status(const void* fused_ws);

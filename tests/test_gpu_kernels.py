@@ -485,7 +485,8 @@ def test_attn_fwd(ops, B, H, Lq, Lk, causal, q_log2):
     vd = dk[:, :, 2 * D:].view(B, Lk, H, 64)
     o = torch.zeros(B, Lq, H, 64, dtype=torch.bfloat16, device="cuda")
     lse = torch.zeros(B, H, Lq, device="cuda")
-    ops.attn_fwd(qd, kd, vd, o, lse, causal=causal, q_log2=q_log2)
+    with _ExpectRoute("occ4_spec" if q_log2 else "occ4"):      # (asked with the argument struct that is then passed)
+        ops.attn_fwd(qd, kd, vd, o, lse, causal=causal, q_log2=q_log2)
     assert maxdiff(lse.cpu(), ref_lse) < 2e-3
     assert maxdiff(o.float().cpu(), ref_o) < 2e-2
 
@@ -511,7 +512,8 @@ def test_attn_fwd_log2_reference_exponent_moves(ops, causal):
     ref_o, ref_lse = _attn_ref(q, k, v, causal, True)
     o = torch.zeros(B, L, H, 64, dtype=torch.bfloat16, device="cuda")
     lse = torch.zeros(B, H, L, device="cuda")
-    ops.attn_fwd(dev(q, torch.bfloat16), dev(k, torch.bfloat16), dev(v, torch.bfloat16), o, lse, causal=causal, q_log2=True)
+    with _ExpectRoute("occ4_spec"):
+        ops.attn_fwd(dev(q, torch.bfloat16), dev(k, torch.bfloat16), dev(v, torch.bfloat16), o, lse, causal=causal, q_log2=True)
     s2 = torch.einsum("blhd,bmhd->bhlm", q.double(), k.double())          # base-2 scores
     assert float(s2[:, :, 0:32].min()) > 70 and float(s2[:, :, 32:64].max()) < -70 and float(s2[:, :, 64:96, :128].max()) < 60 < float(s2[:, :, 64:96].max())
     assert torch.isfinite(lse).all() and torch.isfinite(o.float()).all()
@@ -530,6 +532,12 @@ def test_attn_bwd(ops, B, H, Lq, Lk, causal, q_log2, fused):
     visitor of the dQ tiles), ragged last key block / query tile, an all-padding second query block, Lq != Lk."""
     if fused and causal:
         pytest.skip("the fused backward is dense-only")
+    _attn_bwd_case(ops, B, H, Lq, Lk, causal, q_log2, fused, "fused" if fused else "dq_dkv")
+
+
+def _attn_bwd_case(ops, B, H, Lq, Lk, causal, q_log2, fused, route):
+    """One backward call against autograd in fp64 on the CPU; `route`: what the library must answer for the argument struct it is then
+    called with."""
     g = torch.Generator().manual_seed(B * 999 + Lq + 3 * Lk)
     D = H * 64
     qkv_q = _bf(torch.randn(B, Lq, 3 * D, generator=g) * 0.6)
@@ -557,9 +565,10 @@ def test_attn_bwd(ops, B, H, Lq, Lk, causal, q_log2, fused):
     gk = torch.zeros(B, Lk, 3 * D, dtype=torch.bfloat16, device="cuda")
     delta = torch.empty(2, B, H, Lq, device="cuda")
     csq, csv = torch.full((D,), 0.25, device="cuda"), torch.full((D,), -0.5, device="cuda")
-    ops.attn_bwd(qd, kd, vd, o, dev(d_o, torch.bfloat16), lse, delta,
-                 gq[:, :, :D].view(B, Lq, H, 64), gk[:, :, D:2 * D].view(B, Lk, H, 64), gk[:, :, 2 * D:].view(B, Lk, H, 64),
-                 causal=causal, dq_scale=0.5, dq_colsum=csq, dv_colsum=csv, q_log2=q_log2, fused=fused)
+    with _ExpectRoute(route):
+        ops.attn_bwd(qd, kd, vd, o, dev(d_o, torch.bfloat16), lse, delta,
+                     gq[:, :, :D].view(B, Lq, H, 64), gk[:, :, D:2 * D].view(B, Lk, H, 64), gk[:, :, 2 * D:].view(B, Lk, H, 64),
+                     causal=causal, dq_scale=0.5, dq_colsum=csq, dv_colsum=csv, q_log2=q_log2, fused=fused)
     if fused:
         assert ops.attn_bwd_fused_status() == 0
     tol = lambda ref: 2e-2 * max(1.0, float(ref.abs().max()))
@@ -569,6 +578,13 @@ def test_attn_bwd(ops, B, H, Lq, Lk, causal, q_log2, fused):
     assert maxdiff(gq[:, :, :D].float().cpu().view(B, Lq, H, 64), 0.5 * q_grad) < tol(q_grad)
     assert maxdiff(gk[:, :, D:2 * D].float().cpu().view(B, Lk, H, 64), k.grad) < tol(k.grad)
     assert maxdiff(gk[:, :, 2 * D:].float().cpu().view(B, Lk, H, 64), v.grad) < tol(v.grad)
+
+
+@pytest.mark.parametrize("Lk,route", [(1024, "fused"), (896, "dq_dkv")])
+def test_attn_bwd_fused_at_its_natural_threshold(ops, Lk, route):
+    """Without "force": the smallest dense shape with exactly 1024 key-block workgroups and Lq = 256 (B = 8, H = 16, Lk = 1024) runs
+    fused, its neighbour with 896 workgroups stays on the two-kernel form; the error bounds of test_attn_bwd."""
+    _attn_bwd_case(ops, 8, 16, 256, Lk, False, True, True, route)
 
 
 # ------------------------------------------------------------------------------------------------ log-mel (golden F2)
@@ -627,7 +643,8 @@ ROW_BOUNDS = dict(h_out=2e-6, bf16=5e-2, g_out=5e-4, ln_sums=5e-4, fddt_sums=8e-
 
 
 class _ExpectRoute:
-    """While active, every dicow_fddt_ln_fwd / _bwd call first asks the library which body it will run and fails unless it is `want`."""
+    """While active, every dicow_fddt_ln_fwd / _bwd and dicow_attn_fwd / _bwd call first asks the library, with the argument struct it
+    is about to pass, which body it will run and fails unless it is `want`."""
     def __init__(self, want):
         self.want = want
 

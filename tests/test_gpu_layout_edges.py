@@ -360,9 +360,9 @@ def test_gemm_tn_pooled_group(ops):
 
 
 # ================================================================================================ attention
-ATTN_KV_TILE = 64            # attention.hip:28   KV_TILE: keys per tile of the forward and of the dq kernel
-ATTN_Q_BLOCK = 128           # attention.hip:293  query rows per workgroup (4 waves x 32 rows)
-ATTN_BWD_KEY_BLOCK = 128     # attention.hip:628  keys per workgroup of attn_bwd_dkv_kernel / the fused kernel (:1632 nkb = ceil(Lk / 128))
+ATTN_KV_TILE = 64            # attention.hip KV_TILE: keys per tile of the forward and of the dq kernel
+ATTN_Q_BLOCK = 128           # attention.hip attn_fwd_plan: query rows per workgroup (4 waves x 32 rows)
+ATTN_BWD_KEY_BLOCK = 128     # attention.hip KB: keys per workgroup of attn_bwd_dkv_kernel / the fused kernel (attn_bwd_plan: nkb = ceil(Lk / 128))
 DECODE_GROUPS = 64           # attn_decode.hip:18 AD_NG: key groups of a workgroup, group gi takes keys gi, gi + 64, ...
 DECODE_TRIP = 64 * 4         # attn_decode.hip:41,68  AD_NG * UK keys per trip of the key loop (UK = 4 for group <= 6)
 PAD_ROWS = 7                 # Lmax = L + 7

@@ -200,6 +200,120 @@ def test_row_backward_workspace_covers_every_route():
             assert got == grids[0] * 11 * D * 4, (rows, D, got)          # and no more than the largest of them
 
 
+# ------------------------------------------------------------------------------------------------ attention routing
+def _attn_fwd_args(B=2, H=3, Lq=100, Lk=100, q_log2=0, causal=0, **over):
+    from ts_asr_whisper_amd import _lib
+    a = _lib.AttnFwdArgs()
+    a.q = a.k = a.v = a.o = a.lse = _PTR
+    a.B, a.H, a.Lq, a.Lk, a.causal, a.q_log2 = B, H, Lq, Lk, causal, q_log2
+    a.q_rs = a.k_rs = a.v_rs = 3 * H * 64
+    a.o_rs = H * 64
+    a.q_bs, a.k_bs, a.v_bs, a.o_bs = Lq * 3 * H * 64, Lk * 3 * H * 64, Lk * 3 * H * 64, Lq * H * 64
+    for k, v in over.items():
+        setattr(a, k, v)
+    return a
+
+
+def _attn_bwd_args(B=8, H=16, Lq=256, Lk=1024, causal=0, fused_mode=0, ws="exact", colsums=False, cs_ws=True, **over):
+    """ws: the fused workspace -- "exact" (dicow_attn_bwd_fused_ws_bytes), "short" (one byte less), "unaligned", or None."""
+    from ts_asr_whisper_amd import _lib
+    lib = _lib.lib()
+    a = _lib.AttnBwdArgs()
+    a.q = a.k = a.v = a.o = a.d_o = a.lse = a.delta = a.dq = a.dk = a.dv = _PTR
+    a.B, a.H, a.Lq, a.Lk, a.causal, a.fused_mode, a.dq_scale = B, H, Lq, Lk, causal, fused_mode, 1.0
+    for n in ("q", "k", "v", "o", "do", "dq", "dk", "dv"):
+        setattr(a, n + "_rs", H * 64)
+        setattr(a, n + "_bs", (Lq if n in ("q", "o", "do", "dq") else Lk) * H * 64)
+    if ws is not None:
+        a.fused_ws = _PTR + (8 if ws == "unaligned" else 0)
+        a.fused_ws_bytes = lib.dicow_attn_bwd_fused_ws_bytes(B, H, Lq, Lk) - (1 if ws == "short" else 0)
+    if colsums:
+        a.dq_colsum = a.dv_colsum = _PTR
+        if cs_ws:
+            a.cs_ws, a.cs_ws_bytes = _PTR, lib.dicow_attn_bwd_colsum_ws_bytes(B, H, Lq, Lk)
+    for k, v in over.items():
+        setattr(a, k, v)
+    return a
+
+
+# Expected routes, read off dicow_attn_fwd / dicow_attn_bwd as they stood before the plans existed.
+#   forward   q_log2 -> "occ4_spec", else "occ4"; invalid: a row stride not a multiple of 8, q/k/v batch strides not a multiple of 8 (o: 4),
+#             an empty problem, B or H above 65535
+#   backward  "fused": a 4096-aligned fused_ws of at least dicow_attn_bwd_fused_ws_bytes(), dense, B*H <= 1000, flag area
+#             B*H*ceil(Lq/64)*4 * 4096 < 2^32, and -- unless fused_mode == 1 -- B*H*ceil(Lk/128) >= 1024 and Lq >= 256; else "dq_dkv";
+#             invalid: fused_ws not 4096-aligned, column sums without cs_ws, a stride not a multiple of 4
+_ATTN_FWD_ROUTES = [
+    (dict(q_log2=0), "occ4"), (dict(q_log2=1), "occ4_spec"), (dict(q_log2=1, causal=1), "occ4_spec"), (dict(causal=1), "occ4"),
+    (dict(B=65535, H=1), "occ4"), (dict(B=1, H=65535), "occ4"), (dict(B=65536, H=1), None), (dict(B=1, H=65536), None),
+    (dict(q_rs=3 * 192 + 4), None), (dict(o_rs=12), None), (dict(k_bs=100 * 576 + 4), None), (dict(o_bs=100 * 192 + 4), "occ4"),
+    (dict(o_bs=100 * 192 + 2), None), (dict(B=0), None), (dict(H=0), None), (dict(Lq=0), None), (dict(Lk=0), None), (dict(q=None), None),
+]
+_ATTN_BWD_ROUTES = [
+    (dict(), "fused"), (dict(causal=1), "dq_dkv"),                                             # 8 x 16 pairs x 8 key blocks = 1024 workgroups
+    (dict(Lk=896), "dq_dkv"), (dict(B=1, H=341, Lk=384), "dq_dkv"), (dict(B=2, H=256, Lk=256), "fused"),      # 896, 1023, 1024 workgroups
+    (dict(Lq=255), "dq_dkv"), (dict(Lq=256), "fused"),
+    (dict(B=8, H=125, Lk=256), "fused"), (dict(B=7, H=143, Lk=256), "dq_dkv"),                 # 1000 and 1001 pairs
+    (dict(B=1, H=2, Lq=128, Lk=64), "dq_dkv"), (dict(B=1, H=2, Lq=128, Lk=64, fused_mode=1), "fused"),       # fused_mode 1 lifts both size thresholds
+    (dict(Lq=255, fused_mode=1), "fused"), (dict(Lk=896, fused_mode=1), "fused"),
+    (dict(fused_mode=1, causal=1), "dq_dkv"), (dict(B=7, H=143, Lk=256, fused_mode=1), "dq_dkv"),            # ... and nothing else
+    (dict(fused_mode=1, ws=None), "dq_dkv"), (dict(fused_mode=1, ws="short"), "dq_dkv"),
+    (dict(B=8, H=125, Lq=16769, Lk=256, fused_mode=1), "dq_dkv"),
+    (dict(ws=None), "dq_dkv"), (dict(ws="short"), "dq_dkv"), (dict(ws="exact"), "fused"), (dict(ws="unaligned"), None),
+    (dict(fused_mode=1, ws="unaligned"), None), (dict(causal=1, ws="unaligned"), None),
+    (dict(B=8, H=125, Lq=16768, Lk=256), "fused"), (dict(B=8, H=125, Lq=16769, Lk=256), "dq_dkv"),          # the 2^32-byte flag area
+    (dict(colsums=True), "fused"), (dict(colsums=True, ws=None), "dq_dkv"), (dict(colsums=True, cs_ws=False), None),
+    (dict(colsums=True, cs_ws=False, ws=None), None), (dict(colsums=True, cs_ws_bytes=1), None),
+    (dict(dq_rs=16 * 64 + 2), None), (dict(dv_bs=1024 * 1024 + 2), None), (dict(dk_rs=16 * 64 + 4), "fused"), (dict(q_rs=16 * 64 + 4), None),
+    (dict(Lq=0), None), (dict(dv=None), None),
+]
+
+
+def test_attention_routes_host_logic():
+    """dicow_attn_fwd_route / dicow_attn_bwd_route are host logic (no launch): both sides of every boundary of the dispatch as it stood
+    before it was a plan, and rejected arguments answer NULL."""
+    import ctypes as C
+    from ts_asr_whisper_amd import _lib
+    lib = _lib.lib()
+    for table, build, query, names in ((_ATTN_FWD_ROUTES, _attn_fwd_args, lib.dicow_attn_fwd_route, {"occ4", "occ4_spec"}),
+                                       (_ATTN_BWD_ROUTES, _attn_bwd_args, lib.dicow_attn_bwd_route, {"fused", "dq_dkv"})):
+        seen = set()
+        for kw, want in table:
+            got = query(C.byref(build(**kw)))
+            assert (got.decode() if got is not None else None) == want, (build.__name__, kw, got, want)
+            seen.add(want)
+        assert seen == names | {None}
+        assert query(None) is None
+
+
+def test_attn_bwd_fused_eligible_matches_the_former_python_rule():
+    """dicow_attn_bwd_fused_eligible against the predicate that stood in ops.attn_bwd (moved here verbatim: `want` is True or "force").
+    The two may differ only where the hand-off tiles would reach 2^32 bytes: the library never ran those fused, and ops.attn_bwd
+    no longer allocates a workspace for them."""
+    from ts_asr_whisper_amd import _lib
+    lib = _lib.lib()
+
+    def former(B, H, Lq, Lk, causal, want):
+        return bool(want and not causal and B * H <= 1000 and (want == "force" or (B * H * ((Lk + 127) // 128) >= 1024 and Lq >= 256)))
+
+    guarded, n = [], 0
+    for B, H in ((1, 1), (2, 4), (27, 37), (8, 125), (7, 143)):                    # B*H = 1, 8, 999, 1000, 1001
+        for Lk in (1, 127, 128, 129, 1024, 1500, 131072):
+            for Lq in (1, 255, 256, 1500, 16768, 16769):
+                for causal in (0, 1):
+                    for fused_mode in (0, 1):
+                        got = lib.dicow_attn_bwd_fused_eligible(B, H, Lq, Lk, causal, fused_mode)
+                        want = former(B, H, Lq, Lk, causal, "force" if fused_mode else True)
+                        n += 1
+                        if B * H * ((Lq + 63) // 64) * 4 * 4096 >= 2 ** 32:        # the flag-area guard: 4 KB per (pair, 64-query tile, wave)
+                            if want:
+                                guarded.append((B, H, Lq, Lk, causal, fused_mode))
+                            assert got == 0, (B, H, Lq, Lk, causal, fused_mode)
+                        else:
+                            assert got == int(want), (B, H, Lq, Lk, causal, fused_mode, got, want)
+    assert n == 5 * 7 * 6 * 2 * 2 and guarded
+    assert {(b * h, lq) for b, h, lq, *_ in guarded} == {(999, 16769), (1000, 16769)}
+
+
 def test_no_cpu_fallback_and_oracle_not_imported_by_product():
     src_dir = os.path.join(ROOT, "ts-asr-whisper_amd")
     for fn in os.listdir(src_dir):

@@ -56,21 +56,3 @@ if os.environ.get("ATTN_PROFILE_FUSED"):     # only with a -DATTN_FUSED_PROFILE=
     print("fused bwd: workgroup start times (us after the first), percentiles 10/50/90/100:",
           [round(float(x) / 100, 1) for x in torch.quantile(rec[:, 12] - t0, torch.tensor([0.1, 0.5, 0.9, 1.0], dtype=torch.float64))],
           "; end of the last:", round(float((rec[:, 12] + rec[:, 10]).max() - t0) / 100, 1))
-if os.environ.get("ATTN_PROFILE"):
-    ops.attn_fwd(q, k, v, o, lse, causal=bool(causal)); torch.cuda.synchronize()
-    nblk = B * H * ((Lq + 127) // 128)
-    pr = lse.view(-1).view(torch.int64)[:nblk * 8].view(-1, 8).double().cpu()
-    nt = pr[:, 6].mean()
-    names = ["stage+wait+barrier", "QK mfma + V tr issue", "softmax", "PV", "lgkm+end barrier"]
-    print(f"per k-tile cycles (wave 0, mean over {nblk} workgroups, {nt:.1f} tiles): " +
-          ", ".join(f"{n} {pr[:, i].mean() / nt:.0f}" for i, n in enumerate(names)) + f"; loop total {pr[:,5].mean()/nt:.0f}/tile; epilogue {pr[:,7].mean():.0f}")
-if os.environ.get("ATTN_PROFILE_DKV"):      # only with a build of the stamped dkv kernel (commit 948e096: -DATTN_PROFILE)
-    ops.attn_bwd(q, k, v, o, d_o, lse, delta, dq, dk, dv, causal=bool(causal), dq_scale=0.125); torch.cuda.synchronize()
-    nblk = B * H * ((Lk + 127) // 128)
-    rows = (nblk + 39) // 40
-    raw = dqkv.view(-1, 3 * D)[:rows, :D].contiguous().view(torch.int64).view(-1, 8)[:nblk].double().cpu()   # 64-byte records in the dq columns
-    nt = raw[:, 3].mean()
-    names = ["vmcnt wait + barrier", "q-block 0", "q-block 1"]
-    print(f"dkv per q-tile cycles (wave 0, {nt:.1f} tiles): " + ", ".join(f"{n} {raw[:, i].mean() / nt:.0f}" for i, n in enumerate(names)) +
-          f"; sum {raw[:, :3].sum(1).mean() / nt:.0f}/tile; loop total {raw[:, 4].mean():.0f} cycles in {raw[:, 5].mean() / 100:.1f} us "
-          f"(100 MHz s_memrealtime) = {raw[:, 4].mean() / raw[:, 5].mean() * 0.1:.2f} GHz")

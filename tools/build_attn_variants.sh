@@ -1,6 +1,9 @@
 #!/bin/bash
 # Build A/B variants of the library that differ only in attention.hip's -D flags (with the measured-and-rejected kernels of csrc/experiments/ compiled in): tools/build_attn_variants.sh name "flags" [name "flags" ...]
-# -> tools/libv_<name>.so (git-ignored; travels to the GPU box).  Used with DICOW_HIP_LIB=... and tools/ab_*.py.
+# -> tools/libva_<name>.so (git-ignored; travels to the GPU box).  Used with DICOW_HIP_LIB=... and tools/ab_*.py.
+# The flags that exist: those of csrc/experiments/attention_fwd_variants.inc (-DATTN_FWD_OCC4=0 sends the forward to its kernels, then
+# -DATTN_FWD_PIPE=1, -DATTN_FWD_WGS=..., -DATTN_FWD_LATE_DMA=..., ...; -DATTN_FWD_NW8=1 the eight-wave form) and -DATTN_FUSED_PROFILE=1
+# (tools/bench_attn.py ATTN_PROFILE_FUSED=1).  The tuning knobs of the shipped kernels are settled and gone from attention.hip.
 set -e
 cd "$(dirname "$0")/../ts-asr-whisper_amd/csrc"
 bash build.sh > /dev/null

@@ -2,7 +2,8 @@
 # Build A/B variants of the library that differ in the -D flags of gemm.hip, fddt_ln.hip, attention.hip and elementwise.hip:
 #   tools/build_var.sh name "gemm flags" "fddt_ln flags" "attention flags" "elementwise flags" [name ...]     ("" = the shipped object)
 # -> tools/libv_<name>.so (git-ignored; travels to the GPU box).  Used with DICOW_HIP_LIB=...   The variant OBJECTS go to gpurun_out/var_build/
-# (never pushed to the GPU box, never in csrc/build/).
+# (never pushed to the GPU box, never in csrc/build/).  attention.hip has one flag left without -DDICOW_EXPERIMENTS: -DATTN_FUSED_PROFILE=1
+# (the variants of the forward kernel need the experiments build: tools/build_attn_variants.sh).
 set -e
 cd "$(dirname "$0")/../ts-asr-whisper_amd/csrc"
 bash build.sh > /dev/null

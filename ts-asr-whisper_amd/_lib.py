@@ -171,6 +171,7 @@ _SIGS = {
     "dicow_lora_wgrad": [C.POINTER(LoraWgradArgs), c_vp],
     "dicow_attn_bwd": [C.POINTER(AttnBwdArgs), c_vp],
     "dicow_attn_bwd_fused_status": [c_vp],
+    "dicow_attn_bwd_fused_eligible": [c_i, c_i, c_i, c_i, c_i, c_i],
     "dicow_ce_loss_fwd": [C.POINTER(CeArgs), c_vp],
     "dicow_ce_loss_bwd": [C.POINTER(CeArgs), c_vp, c_vp],
     "dicow_ctc_loss_fwd": [C.POINTER(CtcArgs), c_vp],
@@ -282,6 +283,8 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
 _SIGS_STR = {   # functions returning const char* (a static name, or NULL)
     "dicow_fddt_ln_fwd_route": [C.POINTER(FddtLnFwdArgs)],
     "dicow_fddt_ln_bwd_route": [C.POINTER(FddtLnBwdArgs)],
+    "dicow_attn_fwd_route": [C.POINTER(AttnFwdArgs)],
+    "dicow_attn_bwd_route": [C.POINTER(AttnBwdArgs)],
 }
 
 

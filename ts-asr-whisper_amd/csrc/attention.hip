@@ -16,13 +16,8 @@
 // the source address (K: ds_read_b128 conflict-free; V: tr-read conflict-free).
 #include "common.h"
 #include <type_traits>
-#include <stdlib.h>
 
 typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void gbl_void_t;
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-    __builtin_amdgcn_global_load_lds((gbl_void_t*)gsrc, (lds_void_t*)lds_dst, 16, 0, 0);
-}
 
 #define HD 64
 #define KV_TILE 64
@@ -81,36 +76,10 @@ __device__ __forceinline__ void dma4x(unsigned lds_addr, __amdgpu_buffer_rsrc_t 
     if constexpr (SC) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen sc0 sc1 lds" :: "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
     else asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds" :: "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
 }
-template <int NI = 2>
 __device__ __forceinline__ void stage_tile_x(const tile_src_t& t, int row0, char* lds, int wave) {
-    const unsigned so = (unsigned)(row0 * t.row_bytes), la = (unsigned)(uintptr_t)lds + (unsigned)(wave * NI) * 1024u;
+    const unsigned so = (unsigned)(row0 * t.row_bytes), la = (unsigned)(uintptr_t)lds + (unsigned)(wave * 2) * 1024u;
 #pragma unroll
-    for (int i = 0; i < NI; ++i) dma16x<0>(la + i * 1024u, t.rs, t.vo[i], so);
-}
-
-// 8 transposing reads (one 32-key block x 64 d) + wait, as ONE asm statement (see gemm.hip for the rationale).
-// a0/a1 = lane base addresses for d-block 0/1; OFF selects the 32-key block inside the tile.
-template <int OFF>
-__device__ __forceinline__ void tr_read_block(bf16x8_t (&f)[2][2], unsigned a0, unsigned a1) {
-    bf16x4_t r0, r1, r2, r3, r4, r5, r6, r7;
-    asm volatile(
-        "ds_read_b64_tr_b16 %0, %8 offset:%10\n\t"
-        "ds_read_b64_tr_b16 %1, %8 offset:%11\n\t"
-        "ds_read_b64_tr_b16 %2, %9 offset:%10\n\t"
-        "ds_read_b64_tr_b16 %3, %9 offset:%11\n\t"
-        "ds_read_b64_tr_b16 %4, %8 offset:%12\n\t"
-        "ds_read_b64_tr_b16 %5, %8 offset:%13\n\t"
-        "ds_read_b64_tr_b16 %6, %9 offset:%12\n\t"
-        "ds_read_b64_tr_b16 %7, %9 offset:%13\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7)
-        : "v"(a0), "v"(a1), "i"(OFF), "i"(OFF + 1024), "i"(OFF + 2048), "i"(OFF + 3072)
-        : "memory");
-    // f[x][dblk]
-    f[0][0] = __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7);
-    f[0][1] = __builtin_shufflevector(r2, r3, 0, 1, 2, 3, 4, 5, 6, 7);
-    f[1][0] = __builtin_shufflevector(r4, r5, 0, 1, 2, 3, 4, 5, 6, 7);
-    f[1][1] = __builtin_shufflevector(r6, r7, 0, 1, 2, 3, 4, 5, 6, 7);
+    for (int i = 0; i < 2; ++i) dma16x<0>(la + i * 1024u, t.rs, t.vo[i], so);
 }
 
 // lane base address (bytes, LDS) of the transposing read for d-block `dblk` of a V-style tile at `s`
@@ -223,68 +192,33 @@ __device__ __forceinline__ void attn_block_coords(int nblk, int H, int B, int& b
     h = bh % H; b = bh / H;
 }
 
-#ifndef ATTN_DKV_JIT
-#define ATTN_DKV_JIT 0
-#endif
-#ifndef ATTN_BWD_DKV_NW8
-#define ATTN_BWD_DKV_NW8 0
-#endif
+// ---- the hook of the experiments: the forward kernels of rounds 1-2 (the A/B baseline) and their launches live in csrc/experiments/
+#define ATTN_NOT_ROUTED 1
 #ifdef DICOW_EXPERIMENTS
-#include "experiments/attention_fwd_variants.inc"      // the measured-and-rejected forward kernels (see the file)
+#include "experiments/attention_fwd_variants.inc"
 #else
-#define ATTN_FWD_NW8 0
-#define ATTN_FWD_PIPE 0
+static inline int attn_fwd_experiment_route(const dicow_attn_fwd_args*, dim3, hipStream_t) { return ATTN_NOT_ROUTED; }
 #endif
 
+template <int N> struct attn_ic { static constexpr int value = N; };
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2n_t;
 
 // ---- four workgroups per CU (round 3).  Every restructuring of the forward loop that costs the third wave per SIMD loses ~12 %
 // (profiles/r03_attn_fwd_variants.txt): the loop lives on the interleave of independent waves.  This form goes the other way:
 // K fragments are read just in time instead of one tile ahead (32 registers less), the ring has two slots (32 KB), so that four
 // workgroups = four waves per SIMD fit (<= 128 VGPRs, 128 KB of LDS).
-#ifndef ATTN_Q_NT
-#define ATTN_Q_NT 0        // nontemporal Q loads / O stores of the four-workgroup forward kernel (each line is touched once)
-#endif
-#ifndef ATTN_O_NT
-#define ATTN_O_NT 0
-#endif
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2n_t;
-#ifndef ATTN_OCC4_TAIL
-#define ATTN_OCC4_TAIL 1   // skip the all-padding second key block of the last tile and the all-padding waves of the last query block
-#endif
-#ifndef ATTN_DQ_WGS
-#define ATTN_DQ_WGS 2      // resident workgroups per CU the dq kernel's registers are cut for (3: 168 VGPRs)
-#endif
-#ifndef ATTN_BWD_TAIL
-#define ATTN_BWD_TAIL 1
-#endif
-#ifndef ATTN_DKV_CTS
-#define ATTN_DKV_CTS 0     // dkv kernel: the ring slot as a COMPILE-TIME constant (tile loop unrolled by two): every LDS address = lane register + immediate
-#endif
-#ifndef ATTN_DKV_1BAR
-#define ATTN_DKV_1BAR 0    // with ATTN_DKV_CTS: ONE barrier per query tile (the next tile is requested after it, not before)
-#endif
-template <int N> struct attn_ic { static constexpr int value = N; };
-#ifndef ATTN_OCC4_PRIO
-#define ATTN_OCC4_PRIO 0   // experiments: 1 = priority 1 in the S^T segment, 2 = in the softmax + PV segment, 3 / 4 = static by workgroup parity
-#endif
-#ifndef ATTN_OCC4_SPEC
-#define ATTN_OCC4_SPEC 1
-#endif
-#ifndef ATTN_OCC4_PKSUM
-#define ATTN_OCC4_PKSUM 0
-#endif
-#ifndef ATTN_FWD_OCC4
-#define ATTN_FWD_OCC4 1
-#endif
-// SPEC (with LOG2): a speculative first pass over all tiles WITHOUT any row maximum -- p = 2^s against exponent zero, which is
+// Base-2 scores (LOG2) run a SPECULATIVE first pass over all tiles WITHOUT any row maximum -- p = 2^s against exponent zero, which is
 // exact while every row's sum stays inside the fp32 / bf16 exponent range; the maximum (25 of the loop's ~140 VALU instructions,
 // and the loop is VALU-bound) was only a guard.  The guard moves to the end: a row whose sum left [2^-100, 2^100] (or is not
 // finite) makes its workgroup vote for a second, ordinary pass (the loop below, with the moving reference exponent) that
 // recomputes the block from scratch.  Both passes run one barrier and one staging step per tile in every wave; the vote is
 // workgroup-uniform.
-template <bool LOG2, bool SPEC = false>
+// Settled, no longer knobs: the base-2 kernel without the speculative pass (-9.4 % with it) and the packed row sums (slower)
+// -- profiles/r03_attn_fwd_variants.txt items 15 and 14; nontemporal Q loads (+0.3 %) / O stores (+4.5 %) and wave priorities by
+// segment or workgroup parity (nothing) -- profiles/r03_cache_policy.txt and DESIGN.md "cache policy of the one-shot streams".
+template <bool LOG2>
 __global__ void __launch_bounds__(256, 4) attn_fwd_occ4_kernel(const dicow_attn_fwd_args a) {
-    static_assert(!SPEC || LOG2, "the speculative pass needs base-2 scores");
+    constexpr bool SPEC = LOG2;
     __shared__ __attribute__((aligned(16))) char smem[4 * TILE_BYTES];      // two (K, V) slots
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -300,8 +234,7 @@ __global__ void __launch_bounds__(256, 4) attn_fwd_occ4_kernel(const dicow_attn_
     bf16x8_t qf[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk)
-        qf[kk] = ATTN_Q_NT ? __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(Q + (int64_t)qrow_c * a.q_rs + kk * 16 + hh * 8))
-                           : *reinterpret_cast<const bf16x8_t*>(Q + (int64_t)qrow_c * a.q_rs + kk * 16 + hh * 8);
+        qf[kk] = *reinterpret_cast<const bf16x8_t*>(Q + (int64_t)qrow_c * a.q_rs + kk * 16 + hh * 8);
     f32x16_t o[2];
 #pragma unroll
     for (int d = 0; d < 2; ++d)
@@ -321,13 +254,12 @@ __global__ void __launch_bounds__(256, 4) attn_fwd_occ4_kernel(const dicow_attn_
     }
     bool general = true;
     if constexpr (SPEC) {
-        if (ATTN_OCC4_PRIO == 3 && (blockIdx.x & 1)) __builtin_amdgcn_s_setprio(1);
-        if (ATTN_OCC4_PRIO == 4 && (blockIdx.x & 2)) __builtin_amdgcn_s_setprio(1);
         // Padding: Lk = 1500 is 23.44 tiles of 64 keys and 11.7 blocks of 128 queries.  When the LAST tile's second key block lies
         // entirely past Lk it is not computed (NKB = 1: 1/48 of the matrix and softmax work of every workgroup), and a wave whose 32
-        // query rows all lie past Lq (the fourth wave of the last query block) only keeps the barriers and its share of the staging.
-        const bool tail_half = ATTN_OCC4_TAIL && !a.causal && nt * KV_TILE - a.Lk >= 32;
-        const bool wave_live = !ATTN_OCC4_TAIL || q0 + wave * 32 < a.Lq;
+        // query rows all lie past Lq (the fourth wave of the last query block) only keeps the barriers and its share of the staging
+        // (DESIGN.md "padding is not computed": encoder forward -0.27 ms, dq + dkv 860 -> 843 us per layer).
+        const bool tail_half = !a.causal && nt * KV_TILE - a.Lk >= 32;
+        const bool wave_live = q0 + wave * 32 < a.Lq;
         auto spec_tile = [&](int t, auto nkb_tag) {
             constexpr int NKB = decltype(nkb_tag)::value;
             char* sK = smem + (t & 1) * 2 * TILE_BYTES;
@@ -341,8 +273,6 @@ __global__ void __launch_bounds__(256, 4) attn_fwd_occ4_kernel(const dicow_attn_
                 stage_tile(srcV, (t + 1) * KV_TILE, nK + TILE_BYTES, wave);
             }
             if (!wave_live) return;
-            if (ATTN_OCC4_PRIO == 1) __builtin_amdgcn_s_setprio(1);
-            if (ATTN_OCC4_PRIO == 2) __builtin_amdgcn_s_setprio(0);
             f32x16_t s[2];
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
@@ -368,8 +298,6 @@ __global__ void __launch_bounds__(256, 4) attn_fwd_occ4_kernel(const dicow_attn_
                         if (key >= a.Lk || (a.causal && key > qrow)) s[kb][r] = -INFINITY;
                     }
             }
-            if (ATTN_OCC4_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-            if (ATTN_OCC4_PRIO == 2) __builtin_amdgcn_s_setprio(1);
             float psum = 0.f;
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
@@ -502,18 +430,6 @@ __global__ void __launch_bounds__(256, 4) attn_fwd_occ4_kernel(const dicow_attn_
 #pragma unroll
                     for (int r = 0; r < 16; ++r) s[kb][r] -= m_ref;
             }
-#if ATTN_OCC4_PKSUM
-            f32x2_t ps2 = {0.f, 0.f};
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const float p0 = __builtin_amdgcn_exp2f(s[kb][r]), p1 = __builtin_amdgcn_exp2f(s[kb][r + 1]);
-                    s[kb][r] = p0; s[kb][r + 1] = p1;
-                    ps2 += f32x2_t{p0, p1};                       // v_pk_add_f32: 16 instructions for the 32 row-sum adds
-                }
-            psum = ps2.x + ps2.y;
-#else
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -522,7 +438,6 @@ __global__ void __launch_bounds__(256, 4) attn_fwd_occ4_kernel(const dicow_attn_
                     s[kb][r] = p;
                     psum += p;
                 }
-#endif
         } else {
         if (__builtin_amdgcn_ballot_w64(mx > m_ref + 8.0f * LN2) != 0) {
             const float m_new = fmaxf(m_ref, mx);
@@ -576,8 +491,7 @@ __global__ void __launch_bounds__(256, 4) attn_fwd_occ4_kernel(const dicow_attn_
                 const int col = d * 32 + 8 * q4 + 4 * hh;
                 const u32x2n_t ov = {pack_bf16x2(o[d][4 * q4] * inv_l, o[d][4 * q4 + 1] * inv_l),
                                      pack_bf16x2(o[d][4 * q4 + 2] * inv_l, o[d][4 * q4 + 3] * inv_l)};
-                if (ATTN_O_NT) __builtin_nontemporal_store(ov, reinterpret_cast<u32x2n_t*>(O + col));
-                else *reinterpret_cast<u32x2n_t*>(O + col) = ov;
+                *reinterpret_cast<u32x2n_t*>(O + col) = ov;
             }
         if (a.lse && hh == 0)
             a.lse[((int64_t)b * a.H + h) * a.Lq + qrow] = LOG2 ? (m_ref + __builtin_amdgcn_logf(l_tot)) * LN2      // (v_log_f32 is log2)
@@ -590,33 +504,42 @@ static int check_strides(int64_t rs, const char* n) {
     return 1;
 }
 
-extern "C" int dicow_attn_fwd(const dicow_attn_fwd_args* a, void* stream) {
+// ------------------------------------------------------------------------------------------------ host dispatch, forward
+// Validate, plan, launch.  attn_fwd_plan / attn_bwd_plan are host arithmetic on the arguments alone -- no HIP call, no validation --
+// shared by the dispatchers, the route queries of the ABI and the workspace sizes.
+struct attn_fwd_plan_t {
+    const char* route;      // "occ4_spec": base-2 scores, speculative first pass; "occ4": natural scores
+    dim3 grid, block;       // one workgroup = 4 waves = 128 query rows of one (batch, head)
+};
+static attn_fwd_plan_t attn_fwd_plan(const dicow_attn_fwd_args* a) {
+    return {a->q_log2 ? "occ4_spec" : "occ4", dim3(dicow_cdiv(a->Lq, 128) * a->H * a->B), dim3(256)};
+}
+
+// One kernel template over LOG2 (q carries log2 e), the instantiation picked by the arguments' q_log2
+#define LAUNCH_LOG2(kernel, log2, grid, block, st, ...) do { \
+    if (log2) hipLaunchKernelGGL(kernel<true>, grid, block, 0, st, __VA_ARGS__); \
+    else hipLaunchKernelGGL(kernel<false>, grid, block, 0, st, __VA_ARGS__); } while (0)
+
+static int attn_fwd_validate(const dicow_attn_fwd_args* a) {
     DICOW_REQUIRE(a && a->q && a->k && a->v && a->o, "attn_fwd: null operand");
     DICOW_REQUIRE(a->B > 0 && a->H > 0 && a->Lq > 0 && a->Lk > 0, "attn_fwd: empty problem");
     DICOW_REQUIRE(a->H <= 65535 && a->B <= 65535, "attn_fwd: B/H too large for the grid");
     if (!check_strides(a->q_rs, "q") || !check_strides(a->k_rs, "k") || !check_strides(a->v_rs, "v") ||
         !check_strides(a->o_rs, "o")) return DICOW_ERR_INVALID;
     DICOW_REQUIRE(a->q_bs % 8 == 0 && a->k_bs % 8 == 0 && a->v_bs % 8 == 0 && a->o_bs % 4 == 0, "attn_fwd: batch strides must keep 16-byte alignment");
-    dim3 grid(dicow_cdiv(a->Lq, 128) * a->H * a->B);
-#ifdef DICOW_EXPERIMENTS
-    static const int ncu = [] { hipDeviceProp_t pr; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&pr, d) == hipSuccess ? pr.multiProcessorCount : 256; }();
-    const int64_t wg8 = (int64_t)dicow_cdiv(a->Lq, 256) * a->H * a->B;
-    if (ATTN_FWD_NW8 && !a->q_log2 && wg8 >= 2 * ncu) {
-        hipLaunchKernelGGL((attn_fwd_kernel<false, 8>), dim3((unsigned)wg8), dim3(512), 0, (hipStream_t)stream, *a);
-        DICOW_CHECK_LAUNCH("attn_fwd (8 waves)");
-        return DICOW_OK;
-    }
-    if (!ATTN_FWD_OCC4) {
-        if (a->q_log2) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, *a);
-        else if (ATTN_FWD_PIPE && !a->causal) hipLaunchKernelGGL(attn_fwd_pipe_kernel, grid, dim3(256), 0, (hipStream_t)stream, *a);
-        else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, *a);
-        DICOW_CHECK_LAUNCH("attn_fwd (experiment)");
-        return DICOW_OK;
-    }
-#endif
-    if (a->q_log2 && ATTN_OCC4_SPEC) hipLaunchKernelGGL((attn_fwd_occ4_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, *a);
-    else if (a->q_log2) hipLaunchKernelGGL((attn_fwd_occ4_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, *a);
-    else hipLaunchKernelGGL((attn_fwd_occ4_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, *a);
+    return DICOW_OK;
+}
+
+extern "C" const char* dicow_attn_fwd_route(const dicow_attn_fwd_args* a) {
+    return attn_fwd_validate(a) == DICOW_OK ? attn_fwd_plan(a).route : nullptr;
+}
+
+extern "C" int dicow_attn_fwd(const dicow_attn_fwd_args* a, void* stream) {
+    if (const int rc = attn_fwd_validate(a)) return rc;
+    const attn_fwd_plan_t p = attn_fwd_plan(a);
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int rc = attn_fwd_experiment_route(a, p.grid, st); rc != ATTN_NOT_ROUTED) return rc;
+    LAUNCH_LOG2(attn_fwd_occ4_kernel, a->q_log2, p.grid, p.block, st, *a);
     DICOW_CHECK_LAUNCH("attn_fwd");
     return DICOW_OK;
 }
@@ -639,33 +562,10 @@ __device__ __forceinline__ unsigned tr_base_u(const char* s, int lane, int dblk,
     return (unsigned)(uintptr_t)(s + row * 128 + (c << 4) + ((u & 1) << 3));
 }
 
-// 8 transposing reads of one 32-row block (rows OFF/128 .. +31) x 64 columns; f[x][dblk], x = 16-row half
-template <int OFF>
-__device__ __forceinline__ void tr_read_block_u(bf16x8_t (&f)[2][2], unsigned a00, unsigned a01, unsigned a10, unsigned a11) {
-    // a{dblk}{sec}
-    bf16x4_t r0, r1, r2, r3, r4, r5, r6, r7;
-    asm volatile(
-        "ds_read_b64_tr_b16 %0, %8 offset:%12\n\t"
-        "ds_read_b64_tr_b16 %1, %9 offset:%12\n\t"
-        "ds_read_b64_tr_b16 %2, %10 offset:%12\n\t"
-        "ds_read_b64_tr_b16 %3, %11 offset:%12\n\t"
-        "ds_read_b64_tr_b16 %4, %8 offset:%13\n\t"
-        "ds_read_b64_tr_b16 %5, %9 offset:%13\n\t"
-        "ds_read_b64_tr_b16 %6, %10 offset:%13\n\t"
-        "ds_read_b64_tr_b16 %7, %11 offset:%13\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7)
-        : "v"(a00), "v"(a01), "v"(a10), "v"(a11), "i"(OFF), "i"(OFF + 2048)
-        : "memory");
-    f[0][0] = __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7);
-    f[0][1] = __builtin_shufflevector(r2, r3, 0, 1, 2, 3, 4, 5, 6, 7);
-    f[1][0] = __builtin_shufflevector(r4, r5, 0, 1, 2, 3, 4, 5, 6, 7);
-    f[1][1] = __builtin_shufflevector(r6, r7, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 // ------------------------------------------------------------------------------------------------ dQ
+// (two resident workgroups per CU: held to the 168 VGPRs of a third one this kernel spills 332 bytes -- profiles/r03_attn_bwd_variants.txt item 4)
 template <bool LOG2>        // q carries log2 e (compile-time: the per-score multiply in front of the exponential disappears)
-__global__ void __launch_bounds__(256, ATTN_DQ_WGS) attn_bwd_dq_kernel(const dicow_attn_bwd_args a) {
+__global__ void __launch_bounds__(256, 2) attn_bwd_dq_kernel(const dicow_attn_bwd_args a) {
     __shared__ __attribute__((aligned(16))) char smem[4 * TILE_BYTES];      // K0 V0 K1 V1 (U images)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -730,8 +630,8 @@ __global__ void __launch_bounds__(256, ATTN_DQ_WGS) attn_bwd_dq_kernel(const dic
     stage_tile(srcV, 0, smem + TILE_BYTES, wave);
     // (padding, as in attn_fwd_occ4_kernel: the last tile's all-padding second key block is not computed, an all-padding wave of the
     // last query block keeps only the barriers and its share of the staging)
-    const bool tail_half = ATTN_BWD_TAIL && !a.causal && nt * KV_TILE - a.Lk >= 32;
-    const bool wave_live = !ATTN_BWD_TAIL || q0 + wave * 32 < a.Lq;
+    const bool tail_half = !a.causal && nt * KV_TILE - a.Lk >= 32;
+    const bool wave_live = q0 + wave * 32 < a.Lq;
     auto dq_tile = [&](int t, auto nkb_tag) {
         constexpr int NKB = decltype(nkb_tag)::value;
         char* sK = smem + (t & 1) * 2 * TILE_BYTES;
@@ -834,17 +734,21 @@ __global__ void __launch_bounds__(256, ATTN_DQ_WGS) attn_bwd_dq_kernel(const dic
 }
 
 // ------------------------------------------------------------------------------------------------ dK, dV
-// lse / delta of a 64-query tile -> LDS (one 4-byte DMA per lane; waves 0/2 fetch lse, waves 1/3 delta, so every wave
-// issues the same number of VMEM ops and one counted vmcnt serves all)
-__device__ __forceinline__ void stage_stats64(const float* lse, const float* delta, int q0, int Lq, char* dst, int wave, int lane) {
+// -lse / -delta of a 64-query tile -> LDS: one 4-byte DMA per lane (waves 0 / 2 fetch lse, waves 1 / 3 delta, so every wave issues the
+// same number of VMEM instructions and one counted vmcnt serves all).  rs: one descriptor over this (batch, head)'s rows of both planes of
+// the workspace; plane: this wave's plane offset.  (The callers build the two themselves: handed over in a struct they compile to other code.)
+__device__ __forceinline__ void stage_stats_x(__amdgpu_buffer_rsrc_t rs, unsigned plane, int q0, int Lq, char* dst, int wave, int lane) {
     int q = q0 + lane; q = q < Lq ? q : Lq - 1;
-    const float* src = (wave & 1) ? delta + q : lse + q;
-    __builtin_amdgcn_global_load_lds((gbl_void_t*)src, (lds_void_t*)(dst + (wave & 1) * 256), 4, 0, 0);
+    dma4x<0>((unsigned)(uintptr_t)dst + (unsigned)(wave & 1) * 256u, rs, plane + (unsigned)q * 4u, 0u);
 }
 
-template <int NW, bool LOG2>      // NW waves = NW * 32 keys per workgroup, sharing each Q / dO tile (8: half the DMA instructions per wave); LOG2 as in attn_bwd_dq_kernel
-__global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : (ATTN_DKV_JIT ? 3 : 2)) attn_bwd_dkv_kernel(const dicow_attn_bwd_args a) {
-    constexpr int KB = NW * 32, NI = 8 / NW;
+// One workgroup = 4 waves = 128 keys, sharing each Q / dO tile, two workgroups per CU.  Measured and removed (the sources are in the parent
+// of the commit that removed them): eight waves = 256 keys, 3 % slower, and a third wave per SIMD on just-in-time fragments, equal
+// (profiles/r03_attn_bwd_variants.txt items 2 and 4); the ring slot as a compile-time constant, with one barrier per tile or two, equal
+// (profiles/r04_attn_bwd_variants.txt).
+template <bool LOG2>        // as in attn_bwd_dq_kernel
+__global__ void __launch_bounds__(256, 2) attn_bwd_dkv_kernel(const dicow_attn_bwd_args a) {
+    constexpr int KB = 128;
     __shared__ __attribute__((aligned(16))) char smem[4 * TILE_BYTES + 1024];   // Q0 dO0 Q1 dO1 (U images) + lse/delta x2
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -856,8 +760,11 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : (ATTN_DKV_JIT ? 3 : 2))
     const unsigned short* K = reinterpret_cast<const unsigned short*>(a.k) + (int64_t)b * a.k_bs + h * HD;
     const unsigned short* V = reinterpret_cast<const unsigned short*>(a.v) + (int64_t)b * a.v_bs + h * HD;
     const unsigned short* dO = reinterpret_cast<const unsigned short*>(a.d_o) + (int64_t)b * a.do_bs + h * HD;
+    // (`lse` has had no reader since the statistics travel through one descriptor over both planes; the line stays because without it the
+    // compiler orders this prologue's address arithmetic differently -- other code than the one measured, profiles/r09_attn_dispatch_refactor_ab.txt)
     const float* lse = a.delta + (int64_t)a.B * a.H * a.Lq + ((int64_t)b * a.H + h) * a.Lq;     // -lse plane of the workspace
     const float* delta = a.delta + ((int64_t)b * a.H + h) * a.Lq;                                // -delta plane
+    (void)lse;
 
     // this wave's 32 keys as B operands (column = key, k-slots = d)
     const int key = kblk0 + wave * 32 + (lane & 31);
@@ -879,21 +786,17 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : (ATTN_DKV_JIT ? 3 : 2))
 
     const int t0 = a.causal ? (kblk0 / KV_TILE) : 0;                 // query tiles entirely before the key block see none of it
     const int nt = (a.Lq + KV_TILE - 1) / KV_TILE;
-    const tile_src_t srcQ = make_tile_src<SWZ_U, NI>(Q, a.q_rs, a.Lq, wave, lane), srcdO = make_tile_src<SWZ_U, NI>(dO, a.do_rs, a.Lq, wave, lane);
+    const tile_src_t srcQ = make_tile_src<SWZ_U>(Q, a.q_rs, a.Lq, wave, lane), srcdO = make_tile_src<SWZ_U>(dO, a.do_rs, a.Lq, wave, lane);
     // (round 6: the DMA is issued from inline assembly -- see dma16x: the compiler's own LDS-DMA made it wait for the NEXT tile's DMA in
     // front of the first seed read of every block)
     __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0) as a builtin: the compiler's scoreboard learns that the K / V fragment loads are done
     const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(delta), 0,
                                                                          (unsigned)(((int64_t)a.B * a.H * a.Lq + a.Lq) * 4), 0x00020000);
     const unsigned stat_plane = (wave & 1) ? 0u : (unsigned)((int64_t)a.B * a.H * a.Lq * 4);
-    auto stage_stats_x = [&](int q0, char* dst) {
-        int q = q0 + lane; q = q < a.Lq ? q : a.Lq - 1;
-        dma4x<0>((unsigned)(uintptr_t)dst + (unsigned)(wave & 1) * 256u, rsS, stat_plane + (unsigned)q * 4u, 0u);
-    };
     if (t0 < nt) {
-        stage_tile_x<NI>(srcQ, t0 * KV_TILE, smem, wave);
-        stage_tile_x<NI>(srcdO, t0 * KV_TILE, smem + TILE_BYTES, wave);
-        stage_stats_x(t0 * KV_TILE, smem + 4 * TILE_BYTES);
+        stage_tile_x(srcQ, t0 * KV_TILE, smem, wave);
+        stage_tile_x(srcdO, t0 * KV_TILE, smem + TILE_BYTES, wave);
+        stage_stats_x(rsS, stat_plane, t0 * KV_TILE, a.Lq, smem + 4 * TILE_BYTES, wave, lane);
     }
     // lane-derived row-fragment offsets (swizzle XORs) computed once: plain VALU instructions share the SIMD's issue port
     // with the MFMAs, so per-tile address arithmetic is pure loss
@@ -906,21 +809,18 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : (ATTN_DKV_JIT ? 3 : 2))
     const unsigned qb10 = tr_base_u(smem, lane, 1, 0), qb11 = tr_base_u(smem, lane, 1, 1);
     // (padding, as in the other attention kernels: the all-padding second query block of the last tile is not computed; a wave whose
     // 32 keys all lie past Lk keeps only the barriers and its share of the staging)
-    const bool tail_half = ATTN_BWD_TAIL && nt * KV_TILE - a.Lq >= 32 && nt - 1 > t0;
-    const bool wave_live = !ATTN_BWD_TAIL || kblk0 + wave * 32 < a.Lk;
-#if ATTN_DKV_CTS
-#include "experiments/attention_dkv_cts.inc"       // compile-time ring slot / one barrier per tile: measured equal (profiles/r04_attn_bwd_variants.txt)
-#else
+    const bool tail_half = nt * KV_TILE - a.Lq >= 32 && nt - 1 > t0;
+    const bool wave_live = kblk0 + wave * 32 < a.Lk;
     auto dkv_tile = [&](int t, auto nqb_tag) {
         constexpr int NQB = decltype(nqb_tag)::value;
         char* sQ = smem + ((t - t0) & 1) * 2 * TILE_BYTES;
         char* sdO = sQ + TILE_BYTES;
         if (t + 1 < nt) {
             char* nQ = smem + ((t - t0 + 1) & 1) * 2 * TILE_BYTES;
-            stage_tile_x<NI>(srcQ, (t + 1) * KV_TILE, nQ, wave);
-            stage_tile_x<NI>(srcdO, (t + 1) * KV_TILE, nQ + TILE_BYTES, wave);
-            stage_stats_x((t + 1) * KV_TILE, smem + 4 * TILE_BYTES + ((t - t0 + 1) & 1) * 512);
-            asm volatile("s_waitcnt vmcnt(%0)" :: "i"(2 * NI + 1) : "memory");     // this tile landed; the next one (2 NI tile pieces + 1 statistics piece) may fly
+            stage_tile_x(srcQ, (t + 1) * KV_TILE, nQ, wave);
+            stage_tile_x(srcdO, (t + 1) * KV_TILE, nQ + TILE_BYTES, wave);
+            stage_stats_x(rsS, stat_plane, (t + 1) * KV_TILE, a.Lq, smem + 4 * TILE_BYTES + ((t - t0 + 1) & 1) * 512, wave, lane);
+            asm volatile("s_waitcnt vmcnt(5)" ::: "memory");      // this tile landed; the next one (4 tile pieces + 1 statistics piece) may fly
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -933,10 +833,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : (ATTN_DKV_JIT ? 3 : 2))
         const unsigned stg = (unsigned)(((t - t0) & 1) * 2 * TILE_BYTES);
         const unsigned q00 = qb00 + stg, q01 = qb01 + stg, q10 = qb10 + stg, q11 = qb11 + stg;
         const unsigned o00 = q00 + TILE_BYTES, o01 = q01 + TILE_BYTES, o10 = q10 + TILE_BYTES, o11 = q11 + TILE_BYTES;
-#if ATTN_DKV_JIT
-#include "experiments/attention_dkv_jit.inc"       // three waves per SIMD with just-in-time fragments: measured equal (profiles/r03_attn_bwd_variants.txt)
-#else
-#define DKV_QBLOCK(QB)                                                                                                  \
+#define DKV_QBLOCK(QB)                                                                                                 \
         {                                                                                                               \
             tr8_t tdo, tq;                                                                                              \
             tr_issue_u<(QB) * 4096>(tdo, o00, o01, o10, o11);                                                           \
@@ -977,7 +874,6 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : (ATTN_DKV_JIT ? 3 : 2))
                 }                                                                                                       \
             }                                                                                                           \
         }
-#endif
         if (wave_live) {
             DKV_QBLOCK(0)
             if constexpr (NQB == 2) DKV_QBLOCK(1)
@@ -992,9 +888,9 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : (ATTN_DKV_JIT ? 3 : 2))
         for (int t = t0; t < nfull; ++t) dkv_tile(t, attn_ic<2>{});
         if (tail_half) dkv_tile(nt - 1, attn_ic<1>{});
     }
-#endif
     if (a.dv_colsum) {        // v_proj bias gradient, fused: second workspace plane, partial row (b, key block, wave)
-        // partial rows are indexed by 128-key block and wave-in-block whatever the workgroup size (the reduction's layout)
+        // (kb128 = kblk and the test below always holds; both stand as they did when the workgroup size was a template parameter: without
+        // them this kernel comes out five instructions shorter -- other code than the one measured, profiles/r09_attn_dispatch_refactor_ab.txt)
         const int nqb = (a.Lq + 127) / 128, nkb = (a.Lk + 127) / 128;
         const int kb128 = (kblk0 >> 7) + (wave >> 2);
         float* wsr = reinterpret_cast<float*>(a.cs_ws) + (int64_t)a.B * nqb * 4 * a.H * HD +
@@ -1054,12 +950,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : (ATTN_DKV_JIT ? 3 : 2))
 #define FUSED_WS_HDR 4096                    // status words (int[0] = error bits, int[1] = abort), then per-pair XCD ids; flags follow
 #define FUSED_ERR_TIMEOUT 1
 #define FUSED_ERR_XCD 2
-#ifndef ATTN_FUSED_MIN_WGS
-#define ATTN_FUSED_MIN_WGS 1024              // (512: whisper-base B = 8 -- 768 workgroups -- measured in profiles/r06_base_kernel_table.txt)
-#endif
-#ifndef ATTN_FUSED_SPIN
-#define ATTN_FUSED_SPIN (1 << 15)
-#endif
+constexpr int FUSED_SPIN = 1 << 15;          // polls a slow-path wait may take before it raises FUSED_ERR_TIMEOUT (profiles/r06_attn_fused.txt)
 
 // -delta[q] = -rowsum(dO * O) and -lse (base-2 units in q_log2 mode) for every (b, h, q): the seeds of the dP / S accumulators
 // (computed in the dq kernel's prologue in the two-kernel form); 8 lanes per row.  Also clears the header and flags of the workspace.
@@ -1118,7 +1009,7 @@ __device__ __forceinline__ bool fused_wait_flag(__amdgpu_buffer_rsrc_t rsF, unsi
         if ((unsigned)__builtin_amdgcn_readfirstlane((int)f) == expect) return true;
         if ((spin & 63) == 63) {
             const int ab = __hip_atomic_load(status + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__builtin_amdgcn_readfirstlane(ab) != 0 || spin >= ATTN_FUSED_SPIN) {
+            if (__builtin_amdgcn_readfirstlane(ab) != 0 || spin >= FUSED_SPIN) {
                 if ((threadIdx.x & 63) == 0) { atomicOr(status, FUSED_ERR_TIMEOUT); __hip_atomic_store(status + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
                 return false;
             }
@@ -1127,15 +1018,12 @@ __device__ __forceinline__ bool fused_wait_flag(__amdgpu_buffer_rsrc_t rsF, unsi
     }
 }
 
-#ifndef ATTN_FUSED_PROFILE
-#define ATTN_FUSED_PROFILE 0
-#endif
-#ifndef ATTN_FUSED_ABL
-#define ATTN_FUSED_ABL 0      // ablation builds (results are garbage, only the time matters): 1 no hand-off, 2 no dQ product, 4 no dS^T writes, 8 no exponentials, 16 no DMA after the prologue, 32 no dV / dK MFMAs
-#endif
+// ---- instrumentation, -DATTN_FUSED_PROFILE=1 (not a tuning knob; undefined = off): per-workgroup cycle accounting of wave 0 -- stamps 0..8
+// per tile, the deltas to the previous stamp summed over the tiles; a record of 16 int64 per workgroup behind the tiles of the workspace
+// (tools/bench_attn.py ATTN_PROFILE_FUSED=1).  The ablation arms that once stood beside it in the tile body (no hand-off, no dQ product,
+// no dS^T writes, ...: garbage results, only the time mattered) and the reverse walk are gone: profiles/r06_attn_fused.txt holds both.
 #if ATTN_FUSED_PROFILE
-// per-workgroup cycle accounting (wave 0): stamps 0..7 per tile, the deltas to the previous stamp summed over the tiles; record of 16
-// int64 per workgroup behind the tiles of the workspace (tools/bench_attn.py ATTN_PROFILE_FUSED=1)
+#define FPROF_WS_BYTES(workgroups) ((int64_t)(workgroups) * 16 * 8)
 #define FPROF_DECL long long fp_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; int fp_slow = 0; long long fp_prev = __builtin_readcyclecounter(); const long long fp_t0 = fp_prev, fp_r0 = wall_clock64();
 #define FPROF(i) { const long long n_ = __builtin_readcyclecounter(); fp_acc[i] += n_ - fp_prev; fp_prev = n_; }
 #define FPROF_DEP(x) asm volatile("" : "+v"(x));
@@ -1143,6 +1031,7 @@ __device__ __forceinline__ bool fused_wait_flag(__amdgpu_buffer_rsrc_t rsF, unsi
 #define FPROF_END { if (tid == 0) { long long* rec = reinterpret_cast<long long*>(tiles + nflags * 4096) + (long long)blockIdx.x * 16; \
       for (int i = 0; i < 9; ++i) rec[i] = fp_acc[i]; rec[9] = __builtin_readcyclecounter() - fp_t0; rec[10] = wall_clock64() - fp_r0; rec[11] = kblk; rec[12] = fp_r0; rec[13] = fp_slow; } }
 #else
+#define FPROF_WS_BYTES(workgroups) 0
 #define FPROF_DECL
 #define FPROF(i)
 #define FPROF_DEP(x)
@@ -1239,8 +1128,11 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(const dicow_attn
     const unsigned short* K = reinterpret_cast<const unsigned short*>(a.k) + (int64_t)b * a.k_bs + h * HD;
     const unsigned short* V = reinterpret_cast<const unsigned short*>(a.v) + (int64_t)b * a.v_bs + h * HD;
     const unsigned short* dO = reinterpret_cast<const unsigned short*>(a.d_o) + (int64_t)b * a.do_bs + h * HD;
+    // (`lse` has had no reader since the statistics travel through one descriptor over both planes; the line stays because without it the
+    // compiler orders this prologue's address arithmetic differently -- other code than the one measured, profiles/r09_attn_dispatch_refactor_ab.txt)
     const float* lse = a.delta + (int64_t)a.B * a.H * a.Lq + ((int64_t)b * a.H + h) * a.Lq;     // -lse plane of the workspace
     const float* delta = a.delta + ((int64_t)b * a.H + h) * a.Lq;                                // -delta plane
+    (void)lse;
     int* const status = reinterpret_cast<int*>(fws);
     const int pair = b * a.H + h;
 
@@ -1298,32 +1190,20 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(const dicow_attn
     // last of others (balanced).  rank(tile) = (k - j) mod nkb is a fixed function of the shape: the sum order is the same in every run.
     const int R = rstride > 0 ? rstride : nt / nkb;          // tiles between the starts of consecutive key blocks (0: nt < nkb -- every block starts at tile 0)
     const bool rot = R > 0 && R * (nkb - 1) < nt;
-#ifndef ATTN_FUSED_REVERSE
-#define ATTN_FUSED_REVERSE 0      // (measured: the middle blocks 17 -> 14 % of their tiles on the slow path, block 0 -- which then follows the LAST block -- 69 %: no gain)
-#endif
-    // (the rotation runs on a VIRTUAL index vj = nkb - 1 - j: the visitor before key block j on a tile is then key block j - 1, dispatched
-    // BEFORE it -- its lead is the rotation's R tiles plus the dispatch gap instead of minus it; only block 0 follows the last one)
-    const int vj = (rot && ATTN_FUSED_REVERSE) ? nkb - 1 - kblk : kblk;
-    const int s_j = rot ? vj * R : 0;
+    const int s_j = rot ? kblk * R : 0;
     auto tile_of = [&](int i) { const int x = s_j + i; return x >= nt ? x - nt : x; };
 
     const tile_src_t srcQ = make_tile_src<SWZ_U>(Q, a.q_rs, a.Lq, wave, lane), srcdO = make_tile_src<SWZ_U>(dO, a.do_rs, a.Lq, wave, lane);
-    // -lse / -delta of a 64-query tile: one 4-byte DMA per lane (waves 0 / 2 fetch lse, waves 1 / 3 delta: the same number of VMEM
-    // instructions in every wave); one descriptor over this (batch, head)'s rows of both planes of the workspace
     const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(delta), 0,
                                                                          (unsigned)(((int64_t)a.B * a.H * a.Lq + a.Lq) * 4), 0x00020000);
     const unsigned stat_plane = (wave & 1) ? 0u : (unsigned)((int64_t)a.B * a.H * a.Lq * 4);
-    auto stage_stats_x = [&](int q0, char* dst) {
-        int q = q0 + lane; q = q < a.Lq ? q : a.Lq - 1;
-        dma4x<0>((unsigned)(uintptr_t)dst + (unsigned)(wave & 1) * 256u, rsS, stat_plane + (unsigned)q * 4u, 0u);
-    };
     stage_tile_x(srcQ, tile_of(0) * KV_TILE, smem, wave);
     stage_tile_x(srcdO, tile_of(0) * KV_TILE, smem + TILE_BYTES, wave);
-    stage_stats_x(tile_of(0) * KV_TILE, sST);
+    stage_stats_x(rsS, stat_plane, tile_of(0) * KV_TILE, a.Lq, sST, wave, lane);
     if (nt > 1) {
         stage_tile_x(srcQ, tile_of(1) * KV_TILE, smem + 2 * TILE_BYTES, wave);
         stage_tile_x(srcdO, tile_of(1) * KV_TILE, smem + 3 * TILE_BYTES, wave);
-        stage_stats_x(tile_of(1) * KV_TILE, sST + 512);
+        stage_stats_x(rsS, stat_plane, tile_of(1) * KV_TILE, a.Lq, sST + 512, wave, lane);
         asm volatile("s_waitcnt vmcnt(5)" ::: "memory");      // the first tile landed, the second may fly
     } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1340,8 +1220,8 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(const dicow_attn
     const int dsrow = wave * 32 + (lane & 31);
     const int dsw = (dsrow * 128 + 8 * hh) ^ (rev3((dsrow >> 1) & 7) << 4);      // byte offset inside an image
     const unsigned dsr0 = tr_base_u(sDS, lane, qsub, 0), dsr1 = tr_base_u(sDS, lane, qsub, 1);
-    const bool tail_half = ATTN_BWD_TAIL && nt * KV_TILE - a.Lq >= 32 && nt > 1;
-    const bool wave_live = kblk0 + wave * 32 < a.Lk && !((ATTN_FUSED_ABL & 64) && wave == 3);      // (ablation 64: three working waves per workgroup)
+    const bool tail_half = nt * KV_TILE - a.Lq >= 32 && nt > 1;
+    const bool wave_live = kblk0 + wave * 32 < a.Lk;
 
     // hand-off addressing: flag word and 4 KB fragment tile of (pair, tile, this wave)
     unsigned* const flags = reinterpret_cast<unsigned*>(fws + FUSED_WS_HDR);
@@ -1369,7 +1249,7 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(const dicow_attn
     // A visitor needs the one before it to be about one and a half tile times ahead; the rotation puts nt / nkb tiles between them.
     int pub_idx = -1, pub_val = 0;                           // stores in flight: the flag to raise at the next vmcnt(0)
     // rank(t) = (k(t) - j) mod nkb, k(t) = min(nkb - 1, t / R) = the last key block that starts at or before tile t, carried incrementally
-    int rk_k = vj, rk_rem = 0, cur_t = s_j;
+    int rk_k = kblk, rk_rem = 0, cur_t = s_j;
     const unsigned z_addr = (unsigned)(uintptr_t)sZ + (unsigned)wave * 4096u;
 
     FPROF_DECL
@@ -1384,10 +1264,10 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(const dicow_attn
         const bool two_blocks = !(tail_half && t == nt - 1);
         const int q32 = qt0 + qsub * 32;                      // first query of this wave's block of the tile's dQ
         const bool blk_live = q32 < a.Lq;
-        const int rank = rot ? (rk_k >= vj ? rk_k - vj : rk_k + nkb - vj) : kblk;
+        const int rank = rot ? (rk_k >= kblk ? rk_k - kblk : rk_k + nkb - kblk) : kblk;
         const bool first = rank == 0, last = rank == nkb - 1;
         const unsigned fidx = (unsigned)((pair * nt + t) * 4 + wave);
-        const bool handoff = blk_live && !first && !(ATTN_FUSED_ABL & 1);
+        const bool handoff = blk_live && !first;
         // the poll: a 4-byte DMA into LDS nobody waits for before the middle of the A phase.  (NOT a load into a register: the compiler
         // believes an asm output is there at once and is free to copy it -- at the merge of two branches it did, before the load had
         // landed, and the late arrival then overwrote a register that had been given to a dS value.)
@@ -1410,14 +1290,14 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(const dicow_attn
                 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[kk], dp, 0, 0, 0);                                  \
             }                                                                                                           \
             f32x16_t pv, dsv;                                                                                           \
-            _Pragma("unroll") for (int r = 0; r < 16; ++r) pv[r] = (ATTN_FUSED_ABL & 8) ? s[r] : (LOG2 ? __builtin_amdgcn_exp2f(s[r]) : __builtin_amdgcn_exp2f(s[r] * LOG2E)); \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) pv[r] = (LOG2 ? __builtin_amdgcn_exp2f(s[r]) : __builtin_amdgcn_exp2f(s[r] * LOG2E)); \
             if (need_mask) {                                                                                            \
                 _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                        \
                     const int qq = qt0 + (QB) * 32 + 8 * (r >> 2) + 4 * hh + (r & 3);                                   \
                     if (qq >= a.Lq || key >= a.Lk) pv[r] = 0.f;                                                         \
                 }                                                                                                       \
             }                                                                                                           \
-            _Pragma("unroll") for (int r = 0; r < 16; ++r) dsv[r] = (ATTN_FUSED_ABL & 8) ? dp[r] : pv[r] * dp[r];       \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) dsv[r] = pv[r] * dp[r];                                      \
             bf16x8_t qtf[2], dotf[2];                                                                                   \
             _Pragma("unroll") for (int x = 0; x < 2; ++x) {                                                             \
                 tr_wait_h2<0>(tdo, tq);                                                                                 \
@@ -1426,13 +1306,11 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(const dicow_attn
                 const bf16x8_t pf = pack8(pv, 8 * x);                                                                   \
                 const bf16x8_t df = pack8(dsv, 8 * x);                                                                  \
                 const uint4 du = __builtin_bit_cast(uint4, df);                                                         \
-                if (!(ATTN_FUSED_ABL & 4)) {                                                                            \
                 *reinterpret_cast<uint2*>(sDS + (dsw ^ ((4 * (QB) + 2 * x) << 4))) = make_uint2(du.x, du.y);            \
-                *reinterpret_cast<uint2*>(sDS + (dsw ^ ((4 * (QB) + 2 * x + 1) << 4))) = make_uint2(du.z, du.w); }      \
+                *reinterpret_cast<uint2*>(sDS + (dsw ^ ((4 * (QB) + 2 * x + 1) << 4))) = make_uint2(du.z, du.w);        \
                 _Pragma("unroll") for (int d = 0; d < 2; ++d) {                                                         \
-                    if (ATTN_FUSED_ABL & 32) { dv[d][0] += bfbits2f((unsigned short)(dotf[d][0] ^ pf[0])); dk[d][0] += bfbits2f((unsigned short)(qtf[d][0] ^ df[0])); } else { \
                     dv[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dotf[d], pf, dv[d], 0, 0, 0);                       \
-                    dk[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qtf[d], df, dk[d], 0, 0, 0); }                      \
+                    dk[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qtf[d], df, dk[d], 0, 0, 0);                        \
                 }                                                                                                       \
                 if (x == 0) {                     /* the second half's fragments: requested once the first half's MFMAs have read theirs */ \
                     asm volatile("" : "+v"(dv[0]), "+v"(dk[0]), "+v"(dv[1]), "+v"(dk[1]));                               \
@@ -1479,13 +1357,12 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(const dicow_attn
         asm volatile("" ::: "memory");
         FPROF(4)
         // ---- B phase: the next-but-one tile's DMA, the dQ product, the hand-off
-        const bool more = i + 2 < nt && !(ATTN_FUSED_ABL & 16);
-        const bool prod = blk_live && !(ATTN_FUSED_ABL & 2);
+        const bool more = i + 2 < nt;
         // this wave's columns of dS^T: all 16 fragment reads up front, then barrier Y -- once every wave HAS them the image may be
         // rewritten, and the rest of the B phase (the MFMAs, the wait for the sum, the stores) runs un-synchronised, beside the
         // other waves' next A phase instead of in a burst with their stores and DMA
         tr8_t u0, u1;
-        if (prod) {
+        if (blk_live) {
             tr_issue_c<0>(u0, dsr0, dsr1);
             tr_issue_c<8192>(u1, dsr0, dsr1);
         }
@@ -1493,14 +1370,14 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(const dicow_attn
             int t2 = t + 2; t2 = t2 >= nt ? t2 - nt : t2; t2 *= KV_TILE;
             stage_tile_x(srcQ, t2, sQ, wave);
             stage_tile_x(srcdO, t2, sdO, wave);
-            stage_stats_x(t2, sST + SLOT * 512);
+            stage_stats_x(rsS, stat_plane, t2, a.Lq, sST + SLOT * 512, wave, lane);
         }
-        if (prod) { tr_wait<0>(u0); tr_wait<0>(u1); }
+        if (blk_live) { tr_wait<0>(u0); tr_wait<0>(u1); }
         else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                         // ---- barrier Y
         asm volatile("" ::: "memory");
         FPROF(5)
-        if (prod) {
+        if (blk_live) {
             f32x16_t dq;
 #pragma unroll
             for (int r = 0; r < 16; ++r) dq[r] = 0.f;
@@ -1536,8 +1413,7 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(const dicow_attn
                 for (int e = 0; e < 4; ++e) { dq[e] += pr.p0[e]; dq[4 + e] += pr.p1[e]; dq[8 + e] += pr.p2[e]; dq[12 + e] += pr.p3[e]; }
             }
             FPROF_DEP(dq[0])
-            if (ATTN_FUSED_ABL & 1) {
-            } else if (!last) {
+            if (!last) {
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
                     const u32x4f_t sv = {__float_as_uint(dq[4 * q4]), __float_as_uint(dq[4 * q4 + 1]), __float_as_uint(dq[4 * q4 + 2]), __float_as_uint(dq[4 * q4 + 3])};
@@ -1606,18 +1482,62 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_fused_kernel(const dicow_attn
     }
 }
 
-extern "C" int64_t dicow_attn_bwd_colsum_ws_bytes(int B, int H, int Lq, int Lk) {
-    return (int64_t)B * (dicow_cdiv(Lq, 128) + dicow_cdiv(Lk, 128)) * 4 * H * HD * 4;
+// ------------------------------------------------------------------------------------------------ host dispatch, backward
+// When a dense backward runs fused (the shape half of the rule; the other half: the caller passed a workspace that is large enough):
+constexpr int64_t FUSED_MIN_WGS = 1024;                 // key-block workgroups: two rounds of the chip -- below them the two-kernel form stays (512,
+                                                        // whisper-base B = 8 with 768 workgroups, measured in profiles/r06_base_kernel_table.txt)
+constexpr int FUSED_MIN_LQ = 256;                       // ... and 256 queries (four 64-query tiles), part of the same size rule (profiles/r06_attn_fused.txt)
+constexpr int64_t FUSED_MAX_PAIRS = 1000;               // (batch, head) pairs: the per-pair XCD words of the workspace header (FUSED_WS_HDR)
+constexpr int64_t FUSED_MAX_FLAG_AREA = 1ll << 32;      // bytes of hand-off tiles: the kernel addresses them with 32-bit buffer offsets
+// (fused_mode 1 lifts the two size thresholds and nothing else: how the tests reach the fused kernel's edge cases)
+
+struct attn_bwd_plan_t {
+    bool fused_eligible;                // the shape half of the rule
+    bool fused;                         // ... and the workspace is there: attn_bwd_stats_kernel + attn_bwd_fused_kernel; else dq + dkv
+    dim3 dq_grid, dkv_grid;             // two-kernel route: a workgroup per 128 queries / per 128 keys of a (batch, head)
+    int nt, nkb;                        // fused route: 64-query tiles, 128-key blocks
+    int64_t nflags;                     //   hand-off flags = 4 KB hand-off tiles: one per (pair, tile, wave)
+    int n_zero;                         //   words the stats kernel clears: the header and the flags
+    dim3 stats_grid, fused_grid;        //   fused_grid: whole groups of 8 (batch, head) pairs, one pair per XCD
+    int64_t fused_ws_bytes, cs_ws_bytes;
+    int rq, rk;                         // partial rows of the fused column sums (dq plane: per wave of a 128-query block, or per 32-query
+    int64_t dv_plane;                   //   block when fused; dv plane: per wave of a 128-key block) and where the dv plane starts (floats)
+};
+static attn_bwd_plan_t attn_bwd_plan(const dicow_attn_bwd_args* a) {
+    attn_bwd_plan_t p;
+    const int nqb = dicow_cdiv(a->Lq, 128);
+    const int64_t pairs = (int64_t)a->B * a->H, D = (int64_t)a->H * HD;
+    p.nt = dicow_cdiv(a->Lq, KV_TILE);
+    p.nkb = dicow_cdiv(a->Lk, 128);
+    p.nflags = pairs * p.nt * 4;
+    p.n_zero = (int)((FUSED_WS_HDR + p.nflags * 4) / 4);
+    const int64_t stat_threads = pairs * a->Lq * 8;     // 8 lanes per row of delta / lse
+    p.stats_grid = dim3((unsigned)dicow_cdiv(stat_threads > p.n_zero ? stat_threads : p.n_zero, 256));
+    const int64_t fused_wgs = (int64_t)8 * dicow_cdiv(pairs, 8) * p.nkb;
+    p.fused_grid = dim3((unsigned)fused_wgs);
+    p.fused_ws_bytes = FUSED_WS_HDR + ((p.nflags * 4 + 4095) & ~(int64_t)4095) + p.nflags * 4096 + FPROF_WS_BYTES(fused_wgs);
+    p.cs_ws_bytes = (int64_t)a->B * (nqb + p.nkb) * 4 * a->H * HD * 4;
+    p.fused_eligible = !a->causal && pairs <= FUSED_MAX_PAIRS &&
+                       (a->fused_mode == 1 || (p.nkb * pairs >= FUSED_MIN_WGS && a->Lq >= FUSED_MIN_LQ)) &&
+                       p.nflags * 4096 < FUSED_MAX_FLAG_AREA;
+    p.fused = p.fused_eligible && a->fused_ws && a->fused_ws_bytes >= p.fused_ws_bytes;
+    p.dq_grid = dim3((unsigned)(nqb * pairs));
+    p.dkv_grid = dim3((unsigned)(p.nkb * pairs));
+    p.rq = (int)(p.fused ? (int64_t)a->B * 2 * p.nt : (int64_t)a->B * nqb * 4);
+    p.rk = (int)((int64_t)a->B * p.nkb * 4);
+    p.dv_plane = (int64_t)a->B * nqb * 4 * D;
+    return p;
+}
+static attn_bwd_plan_t attn_bwd_shape_plan(int B, int H, int Lq, int Lk, int causal, int fused_mode) {
+    dicow_attn_bwd_args a = {};
+    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.causal = causal; a.fused_mode = fused_mode;
+    return attn_bwd_plan(&a);
 }
 
-extern "C" int64_t dicow_attn_bwd_fused_ws_bytes(int B, int H, int Lq, int Lk) {
-    (void)Lk;
-    const int64_t nflags = (int64_t)B * H * dicow_cdiv(Lq, KV_TILE) * 4;
-    return FUSED_WS_HDR + ((nflags * 4 + 4095) & ~(int64_t)4095) + nflags * 4096
-#if ATTN_FUSED_PROFILE
-           + (int64_t)8 * dicow_cdiv((int64_t)B * H, 8) * dicow_cdiv(Lk, 128) * 128
-#endif
-        ;
+extern "C" int64_t dicow_attn_bwd_colsum_ws_bytes(int B, int H, int Lq, int Lk) { return attn_bwd_shape_plan(B, H, Lq, Lk, 0, 0).cs_ws_bytes; }
+extern "C" int64_t dicow_attn_bwd_fused_ws_bytes(int B, int H, int Lq, int Lk) { return attn_bwd_shape_plan(B, H, Lq, Lk, 0, 0).fused_ws_bytes; }
+extern "C" int dicow_attn_bwd_fused_eligible(int B, int H, int Lq, int Lk, int causal, int fused_mode) {
+    return attn_bwd_shape_plan(B, H, Lq, Lk, causal, fused_mode).fused_eligible ? 1 : 0;
 }
 // error bits a fused launch left in its workspace (0 = fine; read AFTER the stream has been synchronised): 1 = a hand-off wait
 // ran out of its budget, 2 = the key blocks of one (batch, head) were not all on one XCD.  Either way dq is not to be trusted.
@@ -1627,17 +1547,8 @@ extern "C" int dicow_attn_bwd_fused_status(const void* fused_ws) {
     if (hipMemcpy(st, fused_ws, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return st[0];
 }
-static bool attn_bwd_use_fused(const dicow_attn_bwd_args* a) {
-    if (!a->fused_ws || a->causal) return false;
-    const int64_t nkb = dicow_cdiv(a->Lk, 128), wgs = nkb * a->H * a->B;
-    if ((int64_t)a->B * a->H > 1000) return false;                                       // (the header's per-pair words)
-    if (a->fused_mode != 1 && (wgs < ATTN_FUSED_MIN_WGS || a->Lq < 256)) return false;  // below two rounds of the chip the two-kernel form stays
-    const int64_t nflags = (int64_t)a->B * a->H * dicow_cdiv(a->Lq, KV_TILE) * 4;
-    if (nflags * 4096 >= ((int64_t)1 << 32)) return false;
-    return a->fused_ws_bytes >= dicow_attn_bwd_fused_ws_bytes(a->B, a->H, a->Lq, a->Lk);
-}
 
-extern "C" int dicow_attn_bwd(const dicow_attn_bwd_args* a, void* stream) {
+static int attn_bwd_validate(const dicow_attn_bwd_args* a) {
     DICOW_REQUIRE(!(a && (a->dq_colsum || a->dv_colsum)) ||
                   (a->cs_ws && a->cs_ws_bytes >= dicow_attn_bwd_colsum_ws_bytes(a->B, a->H, a->Lq, a->Lk)),
                   "attn_bwd: fused column sums need cs_ws of dicow_attn_bwd_colsum_ws_bytes() bytes");
@@ -1648,66 +1559,45 @@ extern "C" int dicow_attn_bwd(const dicow_attn_bwd_args* a, void* stream) {
                           a->q_bs, a->k_bs, a->v_bs, a->o_bs, a->do_bs, a->dq_bs, a->dk_bs, a->dv_bs};
     for (int i = 0; i < 16; ++i) DICOW_REQUIRE(rs[i] % 4 == 0, "attn_bwd: strides must keep 8-byte alignment");
     DICOW_REQUIRE(a->q_rs % 8 == 0 && a->k_rs % 8 == 0 && a->v_rs % 8 == 0 && a->do_rs % 8 == 0, "attn_bwd: q/k/v/dO row strides %% 8");
-    hipStream_t st = (hipStream_t)stream;
     DICOW_REQUIRE(!a->fused_ws || (((uintptr_t)a->fused_ws & 4095) == 0), "attn_bwd: fused_ws must be 4096-byte aligned");
-    if (attn_bwd_use_fused(a)) {
-        const int nt = dicow_cdiv(a->Lq, KV_TILE), nkb = dicow_cdiv(a->Lk, 128);
-        const int64_t nflags = (int64_t)a->B * a->H * nt * 4;
-        const int n_zero = (int)((FUSED_WS_HDR + nflags * 4) / 4);
-        const int64_t nthr = (int64_t)a->B * a->H * a->Lq * 8;
-        const unsigned sblocks = (unsigned)dicow_cdiv(nthr > n_zero ? nthr : n_zero, 256);
-        char* fws = reinterpret_cast<char*>(a->fused_ws);
-        if (a->q_log2) hipLaunchKernelGGL(attn_bwd_stats_kernel<true>, dim3(sblocks), dim3(256), 0, st, *a, reinterpret_cast<unsigned*>(fws), n_zero);
-        else hipLaunchKernelGGL(attn_bwd_stats_kernel<false>, dim3(sblocks), dim3(256), 0, st, *a, reinterpret_cast<unsigned*>(fws), n_zero);
-        DICOW_CHECK_LAUNCH("attn_bwd_stats");
-        const dim3 grid((unsigned)(8 * dicow_cdiv((int64_t)a->H * a->B, 8) * nkb));      // whole groups of 8 (batch, head) pairs: one pair per XCD
-#ifdef DICOW_ABLATIONS
-        static const int rstride = [] { const char* e = getenv("DICOW_ATTN_FUSED_RSTRIDE"); return e ? atoi(e) : 0; }();      // (diagnostic builds: the tile stride of the rotation)
-#else
-        const int rstride = 0;                                // nt / nkb
-#endif
-        if (a->q_log2) hipLaunchKernelGGL(attn_bwd_fused_kernel<true>, grid, dim3(256), 0, st, *a, fws, nt, nkb, rstride);
-        else hipLaunchKernelGGL(attn_bwd_fused_kernel<false>, grid, dim3(256), 0, st, *a, fws, nt, nkb, rstride);
-        DICOW_CHECK_LAUNCH("attn_bwd_fused");
-        if (a->dq_colsum || a->dv_colsum) {
-            const int64_t D = (int64_t)a->H * HD;
-            const int rq = a->B * 2 * nt, rk = a->B * dicow_cdiv(a->Lk, 128) * 4;
-            const float* ws = reinterpret_cast<const float*>(a->cs_ws);
-            const int64_t dv_plane = (int64_t)a->B * dicow_cdiv(a->Lq, 128) * 4 * D;
-            int rc = DICOW_OK;
-            if (a->dq_colsum && a->dv_colsum && rq == rk) {
-                float* outs[2] = {a->dq_colsum, a->dv_colsum};
-                return dicow_launch_reduce_multi(ws, rq, D, dv_plane, outs, 2, D, st);
-            }
-            if (a->dq_colsum) rc = dicow_launch_reduce_parts(ws, rq, D, a->dq_colsum, D, st);
-            if (rc == DICOW_OK && a->dv_colsum) rc = dicow_launch_reduce_parts(ws + dv_plane, rk, D, a->dv_colsum, D, st);
-            return rc;
-        }
-        return DICOW_OK;
-    }
-    if (a->q_log2) hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, dim3(dicow_cdiv(a->Lq, 128) * a->H * a->B), dim3(256), 0, st, *a);
-    else hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, dim3(dicow_cdiv(a->Lq, 128) * a->H * a->B), dim3(256), 0, st, *a);
-    DICOW_CHECK_LAUNCH("attn_bwd_dq");
-    if (ATTN_BWD_DKV_NW8 && (int64_t)dicow_cdiv(a->Lk, 256) * a->H * a->B >= 1024) {
-        if (a->q_log2) hipLaunchKernelGGL((attn_bwd_dkv_kernel<8, true>), dim3(dicow_cdiv(a->Lk, 256) * a->H * a->B), dim3(512), 0, st, *a);
-        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<8, false>), dim3(dicow_cdiv(a->Lk, 256) * a->H * a->B), dim3(512), 0, st, *a);
-    } else {
-        if (a->q_log2) hipLaunchKernelGGL((attn_bwd_dkv_kernel<4, true>), dim3(dicow_cdiv(a->Lk, 128) * a->H * a->B), dim3(256), 0, st, *a);
-        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<4, false>), dim3(dicow_cdiv(a->Lk, 128) * a->H * a->B), dim3(256), 0, st, *a);
-    }
-    DICOW_CHECK_LAUNCH("attn_bwd_dkv");
-    if (a->dq_colsum || a->dv_colsum) {               // add the per-wave partial rows up (no atomics)
-        const int64_t D = (int64_t)a->H * HD;
-        const int rq = a->B * dicow_cdiv(a->Lq, 128) * 4, rk = a->B * dicow_cdiv(a->Lk, 128) * 4;
-        const float* ws = reinterpret_cast<const float*>(a->cs_ws);
-        int rc = DICOW_OK;
-        if (a->dq_colsum && a->dv_colsum && rq == rk) {       // self-attention: both column sums in ONE reduce launch
-            float* outs[2] = {a->dq_colsum, a->dv_colsum};
-            return dicow_launch_reduce_multi(ws, rq, D, (int64_t)rq * D, outs, 2, D, st);
-        }
-        if (a->dq_colsum) rc = dicow_launch_reduce_parts(ws, rq, D, a->dq_colsum, D, st);
-        if (rc == DICOW_OK && a->dv_colsum) rc = dicow_launch_reduce_parts(ws + (int64_t)rq * D, rk, D, a->dv_colsum, D, st);
-        return rc;
-    }
     return DICOW_OK;
+}
+
+extern "C" const char* dicow_attn_bwd_route(const dicow_attn_bwd_args* a) {
+    return attn_bwd_validate(a) != DICOW_OK ? nullptr : attn_bwd_plan(a).fused ? "fused" : "dq_dkv";
+}
+
+// The fused bias gradients: add the kernels' partial rows up (no atomics); self-attention's two column sums in ONE reduce launch
+static int attn_bwd_reduce_colsums(const dicow_attn_bwd_args* a, int rq, int rk, int64_t dv_plane, hipStream_t st) {
+    const int64_t D = (int64_t)a->H * HD;
+    const float* ws = reinterpret_cast<const float*>(a->cs_ws);
+    if (a->dq_colsum && a->dv_colsum && rq == rk) {
+        float* outs[2] = {a->dq_colsum, a->dv_colsum};
+        return dicow_launch_reduce_multi(ws, rq, D, dv_plane, outs, 2, D, st);
+    }
+    int rc = DICOW_OK;
+    if (a->dq_colsum) rc = dicow_launch_reduce_parts(ws, rq, D, a->dq_colsum, D, st);
+    if (rc == DICOW_OK && a->dv_colsum) rc = dicow_launch_reduce_parts(ws + dv_plane, rk, D, a->dv_colsum, D, st);
+    return rc;
+}
+
+extern "C" int dicow_attn_bwd(const dicow_attn_bwd_args* a, void* stream) {
+    if (const int rc = attn_bwd_validate(a)) return rc;
+    const attn_bwd_plan_t p = attn_bwd_plan(a);
+    const hipStream_t st = (hipStream_t)stream;
+    // (the kernels are named in the order the code object has always held them: the order of first use is the order of instantiation)
+    if (p.fused) {
+        char* fws = reinterpret_cast<char*>(a->fused_ws);
+        LAUNCH_LOG2(attn_bwd_stats_kernel, a->q_log2, p.stats_grid, dim3(256), st, *a, reinterpret_cast<unsigned*>(fws), p.n_zero);
+        DICOW_CHECK_LAUNCH("attn_bwd_stats");
+        // (rstride 0: the rotation's stride is nt / nkb; other strides measured flat, profiles/r06_attn_fused.txt)
+        LAUNCH_LOG2(attn_bwd_fused_kernel, a->q_log2, p.fused_grid, dim3(256), st, *a, fws, p.nt, p.nkb, 0);
+        DICOW_CHECK_LAUNCH("attn_bwd_fused");
+    } else {
+        LAUNCH_LOG2(attn_bwd_dq_kernel, a->q_log2, p.dq_grid, dim3(256), st, *a);
+        DICOW_CHECK_LAUNCH("attn_bwd_dq");
+        LAUNCH_LOG2(attn_bwd_dkv_kernel, a->q_log2, p.dkv_grid, dim3(256), st, *a);
+        DICOW_CHECK_LAUNCH("attn_bwd_dkv");
+    }
+    return (a->dq_colsum || a->dv_colsum) ? attn_bwd_reduce_colsums(a, p.rq, p.rk, p.dv_plane, st) : DICOW_OK;
 }

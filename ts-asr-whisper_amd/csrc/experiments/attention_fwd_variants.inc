@@ -698,3 +698,27 @@ __global__ void __launch_bounds__(256, ATTN_PIPE_WGS) attn_fwd_pipe_kernel(const
 }
 
 #undef PIPE_SGB
+
+// ---- the hook dicow_attn_fwd asks before it launches the shipped kernel (an empty inline in the default build): an A/B build routes
+// -DATTN_FWD_NW8=1 (natural scores, at least two rounds of 256-row workgroups) to the eight-wave form and -DATTN_FWD_OCC4=0 to the
+// three-workgroup kernel (with -DATTN_FWD_PIPE=1: dense natural-score problems to the software-pipelined one).
+#ifndef ATTN_FWD_OCC4
+#define ATTN_FWD_OCC4 1
+#endif
+static int attn_fwd_experiment_route(const dicow_attn_fwd_args* a, dim3 grid, hipStream_t st) {
+    static const int ncu = [] { hipDeviceProp_t pr; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&pr, d) == hipSuccess ? pr.multiProcessorCount : 256; }();
+    const int64_t wg8 = (int64_t)dicow_cdiv(a->Lq, 256) * a->H * a->B;
+    if (ATTN_FWD_NW8 && !a->q_log2 && wg8 >= 2 * ncu) {
+        hipLaunchKernelGGL((attn_fwd_kernel<false, 8>), dim3((unsigned)wg8), dim3(512), 0, st, *a);
+        DICOW_CHECK_LAUNCH("attn_fwd (8 waves)");
+        return DICOW_OK;
+    }
+    if (!ATTN_FWD_OCC4) {
+        if (a->q_log2) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, dim3(256), 0, st, *a);
+        else if (ATTN_FWD_PIPE && !a->causal) hipLaunchKernelGGL(attn_fwd_pipe_kernel, grid, dim3(256), 0, st, *a);
+        else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, dim3(256), 0, st, *a);
+        DICOW_CHECK_LAUNCH("attn_fwd (experiment)");
+        return DICOW_OK;
+    }
+    return ATTN_NOT_ROUTED;
+}

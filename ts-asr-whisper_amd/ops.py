@@ -553,9 +553,10 @@ def attn_bwd(q, k, v, o, d_o, lse, delta, dq, dk, dv, causal=False, dq_scale=1.0
         ws = workspace(L.lib().dicow_attn_bwd_colsum_ws_bytes(a.B, a.H, a.Lq, a.Lk), q.device)
         a.dq_colsum, a.dv_colsum, a.cs_ws, a.cs_ws_bytes = _p(dq_colsum), _p(dv_colsum), ws.data_ptr(), ws.numel()
     want = ATTN_BWD_FUSED if fused is None else fused
-    if want and not causal and a.B * a.H <= 1000 and (want == "force" or (a.B * a.H * ((a.Lk + 127) // 128) >= 1024 and a.Lq >= 256)):
+    a.fused_mode = int(want == "force")
+    if want and L.lib().dicow_attn_bwd_fused_eligible(a.B, a.H, a.Lq, a.Lk, a.causal, a.fused_mode):     # (the rule lives in attn_bwd_plan)
         fws = attn_bwd_fused_ws(a.B, a.H, a.Lq, a.Lk, q.device)
-        a.fused_ws, a.fused_ws_bytes, a.fused_mode = fws.data_ptr(), fws.numel(), int(want == "force")
+        a.fused_ws, a.fused_ws_bytes = fws.data_ptr(), fws.numel()
     L.call_struct("dicow_attn_bwd", a)
 
 
