@@ -533,6 +533,38 @@ int dicow_enrollment_windows(const int32_t* cnt, const int32_t* excl, int S, int
 int dicow_enrollment_mix(float* out, int64_t ld_out, int B, int n, const float* bank, const int64_t* clip_start, const int32_t* plan_dev,
                          const int32_t* plan_host, int n_tracks, const int32_t* clip_len_host, int n_clips, void* stream);
 
+/* Any-rate audio intake (ABI 7, additive): interleaved int16 or mono fp32 samples at any rational rate -> mono fp32 at the model's rate,
+ * in the reference's order (src/data/augmentations.py:401-407): the mean over the channels, then torchaudio.functional.resample with its
+ * defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99).  With g = gcd(orig, new), o = orig / g, n = new / g and the bank
+ * h[p][k], p < n, k < 2 width + o, of that function (built on the host in fp64 and rounded once, ts-asr-whisper_amd/wave_intake.py), only
+ * one contiguous run of taps per phase is non-zero in fp32.  The bank arrives compact: first[p] = the first tap of phase p's run (HOST
+ * int32 [n]) and taps_t[s * n + p] = h[p][first[p] + s] for s < S, S = the longest run, zero behind a shorter one (device fp32, tap-major).
+ * One call resamples n_segs segments that share (o, n).  segs is a HOST int64 [n_segs][3] table of (in_start, in_len, out_start), in
+ * frames of `in` and samples of `out`.  For every segment, with x[q] = the mono value of frame in_start + q for 0 <= q < in_len, else 0:
+ *     out[out_start + j n + p] = fma(t[S-1], x[..], ... fma(t[1], x[j o + first[p] + 1 - width], fma(t[0], x[j o + first[p] - width], 0)))
+ *   for j n + p < ceil(n in_len / o), t[s] = taps_t[s * n + p]: one fmaf per tap, s ascending.  o = n = 1, width 0, one tap of 1.0 is the
+ *   identity (conversion and mixdown only).  in_int16 = 0: `in` is fp32 mono (C = 1, channel -1 or 0).  in_int16 = 1: `in` is int16,
+ *   C <= DICOW_RESAMPLE_MAX_CHANNELS channels interleaved; channel = c takes sample / 32768 of channel c, channel = -1 the mean:
+ *   sample / 32768 per channel, the channel sum (both exact), one correctly rounded division by C -- the bits of torch.mean(pcm / 32768, 0).
+ * Nothing outside a segment is read (in_frames, out_samples: the sizes of the two buffers), nothing outside its ceil(n in_len / o)
+ * output samples is written, and every output sample has one writer and one order of summation: its bits do not depend on
+ * frames_per_tile, the grid, or the other segments of the call.  No atomics; one launch behind one copy, capturable.
+ * Checked on the host before anything is launched (-1, dicow_last_error()): 1 <= o, n <= DICOW_RESAMPLE_MAX_RATIO; 1 <= S <= 2 width + o;
+ * first[p] in [0, 2 width + o); every segment inside the stated buffer sizes, lengths >= 0; the output ranges pairwise disjoint; the
+ * pointers aligned (in, out: their element size; taps_t: 16 bytes; ws: 8 bytes); and the LDS budget: a workgroup keeps the input span of
+ * frames_per_tile whole output frames -- (frames_per_tile - 1) o + (max first - min first) + S samples, plus 12 of padding -- and, when
+ * 4 S n <= DICOW_RESAMPLE_LDS_BYTES / 2, the bank (it is read from memory otherwise) in DICOW_RESAMPLE_LDS_BYTES of LDS.  frames_per_tile = 0 lets
+ * the library choose (about 4096 output samples per tile, or what fits); a ratio whose single frame does not fit is refused, and so is a
+ * frames_per_tile that does not.  in and out must not overlap (unchecked: device memory).  ws: dicow_resample_ws_bytes(n_segs, n) bytes;
+ * the table and first[] are copied there with the stream.  n_segs == 0, or segments that are all empty, launch nothing. */
+#define DICOW_RESAMPLE_LDS_BYTES 49152
+#define DICOW_RESAMPLE_MAX_RATIO 1048576
+#define DICOW_RESAMPLE_MAX_CHANNELS 512
+int64_t dicow_resample_ws_bytes(int n_segs, int n);
+int dicow_resample(const void* in, int in_int16, int C, int channel, int64_t in_frames, float* out, int64_t out_samples, const float* taps_t,
+                   const int32_t* first, int o, int n, int width, int S, const int64_t* segs, int n_segs, int frames_per_tile, void* ws,
+                   int64_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ batch augmentation
  * The collator's training-time augmentations (reference src/data/collators.py:189-214), applied to the batch where it
  * already lives (HBM).  The random decisions are drawn on the host from the torch CPU generator in the reference's

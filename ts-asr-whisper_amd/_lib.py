@@ -75,6 +75,8 @@ DIAR_FRAME, DIAR_BIN, DIAR_WINDOW, DIAR_MAX_SPEAKERS = 320, 1600, 300, 64   # DI
 
 ENR_MIX_MAX_TRACKS = 8          # DICOW_ENR_MIX_MAX_TRACKS: tracks per row of dicow_enrollment_mix
 
+RESAMPLE_LDS_BYTES, RESAMPLE_MAX_RATIO, RESAMPLE_MAX_CHANNELS = 49152, 1 << 20, 512   # DICOW_RESAMPLE_*: dicow_resample's limits
+
 LORA_MAX_R, LORA_MAX_SEG = 192, 24
 LORA_BLOCK, LORA_OUT_F32, LORA_GELU, LORA_MUL_AUX = 1, 2, 4, 8
 
@@ -195,6 +197,7 @@ _SIGS = {
     "dicow_stno_from_counts": [c_vp, c_i, c_i64, c_vp, c_i, c_vp, c_i64, c_vp, c_i64, c_vp],
     "dicow_enrollment_windows": [c_vp, c_vp, c_i, c_i64, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
     "dicow_enrollment_mix": [c_vp, c_i64, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_vp],
+    "dicow_resample": [c_vp, c_i, c_i, c_i, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_i, c_i, c_vp, c_i64, c_vp],
     "dicow_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
     "dicow_fabric_emulate": [c_vp, c_i64, c_d, c_i, c_i, c_vp],
     "dicow_adamw_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_i, c_vp, c_f, c_vp],
@@ -277,6 +280,7 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
     "dicow_diar_table_ws_bytes": [c_i],
     "dicow_diar_targets_ws_bytes": [c_i],
     "dicow_enrollment_windows_ws_bytes": [c_i64, c_i],
+    "dicow_resample_ws_bytes": [c_i, c_i],
 }
 
 

@@ -122,10 +122,13 @@ class EnrollmentBank:
         return cls(torch.cat(flat).to(device), starts, lens, speakers, recording_ids, cut_start, durations, supervisions)
 
     @classmethod
-    def from_dir(cls, enroll_dir, device="cuda", sample_rate: int = SAMPLE_RATE, speaker_of=None, recording_of=None) -> "EnrollmentBank":
+    def from_dir(cls, enroll_dir, device="cuda", sample_rate: int = SAMPLE_RATE, speaker_of=None, recording_of=None,
+                 resample: bool = False) -> "EnrollmentBank":
         """Every ``**/*.wav`` under enroll_dir in sorted order, one single-speaker clip each: the speaker is the name of the file's
         directory and the recording id the file's stem, unless ``speaker_of(path)`` / ``recording_of(path)`` say otherwise.  16-bit mono PCM
-        at 16 kHz only, read as ``NoiseBank.from_dir`` reads (other rates and sample widths are refused)."""
+        at 16 kHz only, read as ``NoiseBank.from_dir`` reads (other rates and sample widths are refused) -- unless ``resample=True``: then a
+        mono file at another rate is read as int16 and brought to ``sample_rate`` on the device (``wave_intake``, one launch per distinct
+        rate).  The audio stays unnormalised either way."""
         root = pathlib.Path(enroll_dir)
         if not root.exists():
             raise IOError(f'Enrollment directory `{enroll_dir}` does not exist')
@@ -134,10 +137,20 @@ class EnrollmentBank:
             raise IOError(f'No .wav file found in the enrollment directory `{enroll_dir}`')
         speaker_of = speaker_of or (lambda p: p.parent.name)
         recording_of = recording_of or (lambda p: p.stem)
-        bank = cls.from_tensors([read_pcm16(f, sample_rate, "EnrollmentBank") for f in files], [speaker_of(f) for f in files],
-                                [recording_of(f) for f in files], device=device)
+        speakers, recordings = [speaker_of(f) for f in files], [recording_of(f) for f in files]
+        if resample:
+            bank = cls._from_files_resampled(files, speakers, recordings, device, sample_rate)
+        else:
+            bank = cls.from_tensors([read_pcm16(f, sample_rate, "EnrollmentBank") for f in files], speakers, recordings, device=device)
         bank.files = files
         return bank
+
+    @classmethod
+    def _from_files_resampled(cls, files, speakers, recordings, device, sample_rate):
+        from . import wave_intake
+        data, starts, lens, _ = wave_intake.bank_from_files(files, sample_rate, device, "EnrollmentBank", mono_only=True,
+                                                           at_rate=lambda pcm: torch.from_numpy(pcm.numpy()[:, 0].astype(np.float32) / 32768.0))
+        return cls(data, starts, lens, speakers, recordings)
 
 
 # ------------------------------------------------------------------------------------------------------------------------ planner

@@ -14,8 +14,9 @@ Python's ``random`` module, as the reference does -- so ``torch.manual_seed(s); 
 would have produced; the plan is a few bytes per row and goes up through the pinned staging slots; the arithmetic runs in the kernel.
 
 Two stated deviations from the reference: a crop of the clip that is all zeros leaves ``audio / 2`` (the reference divides by the crop's
-zero norm and returns NaN on every sample), and clips must already be at the model's sample rate (the reference resamples; MUSAN is
-distributed at 16 kHz).  No CPU fallback: waveforms must be on the GPU.
+zero norm and returns NaN on every sample), and ``NoiseBank.from_dir`` refuses a clip at another sample rate unless it is told to
+resample (``resample=True``, ``wave_intake``; the reference always resamples, and MUSAN is distributed at 16 kHz).  No CPU fallback:
+waveforms must be on the GPU.
 """
 import os
 import pathlib
@@ -99,18 +100,38 @@ class NoiseBank:
         return cls(torch.cat(prepared).to(device), starts, lens)
 
     @classmethod
-    def from_dir(cls, noise_dir, device="cuda", sample_rate: int = 16000) -> "NoiseBank":
+    def from_dir(cls, noise_dir, device="cuda", sample_rate: int = 16000, resample: bool = False) -> "NoiseBank":
         """Every ``**/*.wav`` under noise_dir, in the order ``pathlib.Path(noise_dir).glob('**/*.wav')`` lists them in this call (the list
         the reference builds, augmentations.py:388-393).  16-bit PCM only, read with the standard library and scaled by 1 / 32768 as
-        ``torchaudio.load`` normalises; a file at another rate is refused (no resampling here)."""
+        ``torchaudio.load`` normalises; a file at another rate is refused (no resampling here) unless ``resample=True``: then it is read as
+        int16 and brought to ``sample_rate`` on the device (``wave_intake``: one launch per distinct rate and channel count) in the
+        reference's order, augmentations.py:401-410 -- mono mean, resample, division by the peak of the resampled clip.  Files that
+        already are at ``sample_rate`` are prepared as before, bit for bit."""
         if not os.path.exists(noise_dir):
             raise IOError(f'Noise directory `{noise_dir}` does not exist')
         files = list(pathlib.Path(noise_dir).glob('**/*.wav'))
         if len(files) == 0:
             raise IOError(f'No .wav file found in the noise directory `{noise_dir}`')
-        bank = cls.from_tensors([read_pcm16(f, sample_rate, "NoiseBank") for f in files], device)
+        if resample:
+            bank = cls._from_files_resampled(files, device, sample_rate)
+        else:
+            bank = cls.from_tensors([read_pcm16(f, sample_rate, "NoiseBank") for f in files], device)
         bank.files = files
         return bank
+
+    @classmethod
+    def _from_files_resampled(cls, files, device, sample_rate):
+        from . import wave_intake
+        data, starts, lens, foreign = wave_intake.bank_from_files(
+            files, sample_rate, device, "NoiseBank",
+            lambda pcm: _prepare_clip(torch.from_numpy(pcm.numpy().astype(np.float32) / 32768.0).t().contiguous()))
+        for k in foreign:                                                  # (the clips at sample_rate are normalised already)
+            clip = data[starts[k]:starts[k] + lens[k]]
+            peak = torch.max(torch.abs(clip))
+            if not float(peak) > 0.0:
+                raise ValueError(f"NoiseBank: {files[k]} is all zeros (or NaN): the reference would divide by its zero peak")
+            clip.div_(peak)
+        return cls(data, starts, lens)
 
 
 def plan_background_noise(lengths, bank, prob: float, min_snr_db: int = 0, max_snr_db: int = 15):
