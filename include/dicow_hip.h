@@ -565,6 +565,36 @@ int dicow_resample(const void* in, int in_int16, int C, int channel, int64_t in_
                    const int32_t* first, int o, int n, int width, int S, const int64_t* segs, int n_segs, int frames_per_tile, void* ws,
                    int64_t ws_bytes, void* stream);
 
+/* Scoring what was decoded (ABI 7, additive): a batch of Levenshtein tables over int32 symbol ids -- words or characters mapped to dense ids
+ * on the host (ts-asr-whisper_amd/scoring.py) -- for WER / CER (one pair per utterance; the reference: jiwer, src/utils/evaluation.py:32-79)
+ * and cpWER / tcpWER (one pair per (reference speaker, hypothesis speaker); meeteval, src/utils/wer.py:30-38, 89-97).
+ * ref_ids [n_ref], hyp_ids [n_hyp]: flat device buffers.  ref_iv / hyp_iv: device int32 [n_ref][2] / [n_hyp][2] of (begin, end) in integer
+ * ticks, row q belonging to id q; both NULL = unconstrained, one NULL is refused.  pairs: a HOST int64 [n_pairs][4] table of (ref_start,
+ * ref_len, hyp_start, hyp_len); pairs may share or overlap spans.  out: device int32 [n_pairs][2] = (errors, hits):
+ *   unit costs; cell (i, j) may take the diagonal step -- a hit if ref[i] == hyp[j], a substitution otherwise -- only without intervals or
+ *   when rb < he && hb < re (touching intervals do not overlap); otherwise only insertion and deletion are open.  Among the alignments with
+ *   the fewest errors E the one with the most hits H is taken, the lexicographic minimum of the additive key (E, -H).  The other counts
+ *   follow: I = E - N_ref + H, D = E + H - N_hyp, S = N_ref + N_hyp - 2 H - E.  A length of 0 gives (the other length, 0).
+ * One workgroup per pair; lane t keeps a strip of DICOW_EDIT_K columns in registers and rows run as a skewed pipeline, the strip's right
+ * edge handed to lane t + 1 through LDS; a panel is lanes * DICOW_EDIT_K columns, and a longer sequence goes panel by panel with the
+ * panel's last column, one key per row, in the pair's slice of ws.  The key is symmetric in the two sequences, so either may lie along
+ * the lanes.  lanes: 0 = the library's choice for the call (DICOW_EDIT_LANES if the shorter side of some pair exceeds DICOW_EDIT_LANES_NARROW *
+ * DICOW_EDIT_K symbols, DICOW_EDIT_LANES_NARROW otherwise), or one of the two; along: 0 = per pair whichever makes fewer steps, 1 = ref
+ * along the lanes, 2 = hyp.  Exact integer arithmetic: the result depends on neither, nor on the other pairs of the call.  The key is
+ * packed E * 2^15 - H in int32 when ref_len + hyp_len <= 65535 - DICOW_EDIT_LANES * DICOW_EDIT_K for every pair, E * 2^32 - H in int64 otherwise.
+ * Checked on the host before anything is launched (-1, dicow_last_error()): lengths in [0, DICOW_EDIT_MAX_LEN], spans inside n_ref / n_hyp,
+ * intervals for both sides or neither, lanes / along, pointers and their alignment, ws_bytes.  ws: dicow_edit_distance_ws_bytes(pairs,
+ * n_pairs) bytes, 8-byte aligned: the table (copied there with the stream) and the boundary columns; -1 for a table the call would refuse
+ * for its lengths.  One launch behind one copy, no atomics, capturable (a captured call's table image stays allocated: the copy node reads
+ * it at every replay).  n_pairs == 0 launches nothing. */
+#define DICOW_EDIT_MAX_LEN 65535
+#define DICOW_EDIT_K 8
+#define DICOW_EDIT_LANES 512
+#define DICOW_EDIT_LANES_NARROW 64
+int64_t dicow_edit_distance_ws_bytes(const int64_t* pairs, int n_pairs);
+int dicow_edit_distance(const int32_t* ref_ids, int64_t n_ref, const int32_t* hyp_ids, int64_t n_hyp, const int32_t* ref_iv, const int32_t* hyp_iv,
+                        const int64_t* pairs, int n_pairs, int32_t* out, int lanes, int along, void* ws, int64_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ batch augmentation
  * The collator's training-time augmentations (reference src/data/collators.py:189-214), applied to the batch where it
  * already lives (HBM).  The random decisions are drawn on the host from the torch CPU generator in the reference's

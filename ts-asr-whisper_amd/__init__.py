@@ -19,6 +19,8 @@ from .diar_front_end import (SpeakerSegments, stno_masks, select_enrollment_wind
 from .enrollment_mix import (EnrollmentBank, plan_enrollment_mixtures, mix_enrollments, enrollment_stno,  # noqa: F401
                              EnrollmentMixFrontEnd)
 from .wave_intake import (ResamplePlan, resample_plan, resample_segments, resample, read_wav, load_recording)  # noqa: F401
+from .scoring import (edit_counts, Vocabulary, word_error_counts, error_measures, make_compute_metrics, cp_wer, tcp_wer,  # noqa: F401
+                      pseudo_word_intervals, hungarian)
 from .optim import DiCoWAdamW, clip_grad_norm_, dicow_optimizer  # noqa: F401
 
 __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalGeneration", "SpeakerCommunicationBlock",
@@ -26,4 +28,6 @@ __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalG
            "ctc_greedy_decode", "chunked_ctc_logits", "freeze_for_ctc_pretraining", "NoiseBank", "plan_background_noise", "mix_background_noise",
            "WaveFrontEnd", "SpeakerSegments", "stno_masks", "select_enrollment_windows", "draw_enrollment_window", "MeetingFrontEnd",
            "EnrollmentBank", "plan_enrollment_mixtures", "mix_enrollments", "enrollment_stno", "EnrollmentMixFrontEnd",
-           "ResamplePlan", "resample_plan", "resample_segments", "resample", "read_wav", "load_recording"]
+           "ResamplePlan", "resample_plan", "resample_segments", "resample", "read_wav", "load_recording",
+           "edit_counts", "Vocabulary", "word_error_counts", "error_measures", "make_compute_metrics", "cp_wer", "tcp_wer",
+           "pseudo_word_intervals", "hungarian"]

@@ -77,6 +77,8 @@ ENR_MIX_MAX_TRACKS = 8          # DICOW_ENR_MIX_MAX_TRACKS: tracks per row of di
 
 RESAMPLE_LDS_BYTES, RESAMPLE_MAX_RATIO, RESAMPLE_MAX_CHANNELS = 49152, 1 << 20, 512   # DICOW_RESAMPLE_*: dicow_resample's limits
 
+EDIT_MAX_LEN, EDIT_K, EDIT_LANES, EDIT_LANES_NARROW = 65535, 8, 512, 64   # DICOW_EDIT_*: dicow_edit_distance's limit, strip and workgroups
+
 LORA_MAX_R, LORA_MAX_SEG = 192, 24
 LORA_BLOCK, LORA_OUT_F32, LORA_GELU, LORA_MUL_AUX = 1, 2, 4, 8
 
@@ -198,6 +200,7 @@ _SIGS = {
     "dicow_enrollment_windows": [c_vp, c_vp, c_i, c_i64, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
     "dicow_enrollment_mix": [c_vp, c_i64, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_vp],
     "dicow_resample": [c_vp, c_i, c_i, c_i, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_i, c_i, c_vp, c_i64, c_vp],
+    "dicow_edit_distance": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_i, c_vp, c_i64, c_vp],
     "dicow_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
     "dicow_fabric_emulate": [c_vp, c_i64, c_d, c_i, c_i, c_vp],
     "dicow_adamw_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_i, c_vp, c_f, c_vp],
@@ -281,6 +284,7 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
     "dicow_diar_targets_ws_bytes": [c_i],
     "dicow_enrollment_windows_ws_bytes": [c_i64, c_i],
     "dicow_resample_ws_bytes": [c_i, c_i],
+    "dicow_edit_distance_ws_bytes": [c_vp, c_i],
 }
 
 
