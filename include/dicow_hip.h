@@ -595,6 +595,46 @@ int64_t dicow_edit_distance_ws_bytes(const int64_t* pairs, int n_pairs);
 int dicow_edit_distance(const int32_t* ref_ids, int64_t n_ref, const int32_t* hyp_ids, int64_t n_hyp, const int32_t* ref_iv, const int32_t* hyp_iv,
                         const int64_t* pairs, int n_pairs, int32_t* out, int lanes, int along, void* ws, int64_t ws_bytes, void* stream);
 
+/* Scoring sessions whose speaker labels are not trusted (ABI 7, additive): optimal-reference-combination WER and its time-constrained form
+ * (ORC-WER / tcORC-WER; meeteval's orcwer / tcorcwer, which the reference calls per group of a session, src/utils/wer.py:41-106) for a batch
+ * of independent problems -- one problem is one group of one session.  ref_ids / hyp_ids / ref_iv / hyp_iv: as for dicow_edit_distance.
+ * problems: a HOST int64 [n_problems][4] table of (utt_first, n_utts, stream_first, n_streams), rows of the two HOST int64 tables utts
+ * [..][2] = (ref_start, ref_len), one reference utterance per row in the order they are spoken, and streams [..][2] = (hyp_start, hyp_len),
+ * one hypothesis stream per row.  out: device int32 [n_problems][2] = (errors, hits).  assignment: NULL, or device int32 with one entry per
+ * utterance row, the stream (0 .. n_streams - 1 within its problem) the utterance was given to.
+ *   L[j_0, .., j_{H-1}], 0 <= j_h <= hyp_len_h, holds the key of dicow_edit_distance, errors * 2^15 - hits; at first L = (sum of j_h) * 2^15.
+ *   One utterance of m words: for every stream h, every line of L along axis h (the other indices fixed) takes m Levenshtein row updates
+ *   against stream h, new[0] = old[0] + 2^15, new[j] = min(old[j] + 2^15, new[j-1] + 2^15, old[j-1] + (-1 if the words are equal else 2^15)),
+ *   the diagonal term open only without intervals or when rb < he && hb < re; the table after the utterance is the elementwise minimum of
+ *   the H results.  An utterance of 0 words changes nothing.  The answer is L[hyp_len_0, .., hyp_len_{H-1}]: the minimum over all H^U ways
+ *   to give utterances to streams of the summed keys of dicow_edit_distance(the stream's utterances concatenated, the stream).
+ *   assignment: one that attains this minimum; among equal keys the stream with the smallest index, then the path that entered the
+ *   stream's line earliest; an utterance of 0 words gets stream 0.  It depends on nothing but the problem.  With an assignment two
+ *   problems may not share utterance rows.  No stream: (all reference words, 0), assignment -1.  No utterance: (all hypothesis words, 0).
+ * The streams of a problem lie along the axes in ascending length, so the contiguous axis is the shortest stream.  Launches: one fill, per
+ * utterance step one lane-per-line pass over every axis of every problem that has such an utterance (a column of DICOW_ORC_K + 1 keys in
+ * registers per chunk of DICOW_ORC_K words: one read and one write per cell per chunk) and one elementwise fold, then one that reads the
+ * corners and chases the assignment back; no atomics, no waiting between workgroups, capturable like dicow_edit_distance.
+ * ws: dicow_orc_distance_ws_bytes(...) bytes, 8-byte aligned, at most DICOW_ORC_MAX_WS_BYTES.  With S = the product of (hyp_len_h + 1),
+ * H = n_streams, U = n_utts and r8 = rounding up to 8:  n_problems * DICOW_ORC_DESC_BYTES + (all n_utts) * DICOW_ORC_UTT_BYTES, and for
+ * every problem with H > 0 and U > 0:  r8(4 S) + r8(4 H S)  without assignment,  r8(4 S) + 8 H S + r8(4 S U)  with it.
+ * Checked on the host before anything is launched (-1, dicow_last_error() names the limit): n_streams <= DICOW_ORC_MAX_STREAMS; reference +
+ * hypothesis words of a problem <= DICOW_ORC_MAX_WORDS (the int32 key, DICOW_ORC_K rows of padding included); S <= DICOW_ORC_MAX_STATES;
+ * the workspace <= DICOW_ORC_MAX_WS_BYTES (a call refused for its assignment's records may still run without); spans inside n_ref /
+ * n_hyp; intervals for both sides or neither; pointers and their alignment; ws_bytes.  dicow_orc_distance_ws_bytes returns -1 for tables
+ * the call would refuse for their sizes.  n_problems == 0 launches nothing. */
+#define DICOW_ORC_MAX_STREAMS 8
+#define DICOW_ORC_K 8
+#define DICOW_ORC_MAX_WORDS 65527
+#define DICOW_ORC_MAX_STATES 4194304
+#define DICOW_ORC_MAX_WS_BYTES 1073741824LL
+#define DICOW_ORC_DESC_BYTES 288
+#define DICOW_ORC_UTT_BYTES 16
+int64_t dicow_orc_distance_ws_bytes(const int64_t* problems, int n_problems, const int64_t* utts, const int64_t* streams, int want_assignment);
+int dicow_orc_distance(const int32_t* ref_ids, int64_t n_ref, const int32_t* hyp_ids, int64_t n_hyp, const int32_t* ref_iv, const int32_t* hyp_iv,
+                       const int64_t* problems, int n_problems, const int64_t* utts, const int64_t* streams, int32_t* out, int32_t* assignment,
+                       void* ws, int64_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ batch augmentation
  * The collator's training-time augmentations (reference src/data/collators.py:189-214), applied to the batch where it
  * already lives (HBM).  The random decisions are drawn on the host from the torch CPU generator in the reference's

@@ -20,7 +20,9 @@ from .enrollment_mix import (EnrollmentBank, plan_enrollment_mixtures, mix_enrol
                              EnrollmentMixFrontEnd)
 from .wave_intake import (ResamplePlan, resample_plan, resample_segments, resample, read_wav, load_recording)  # noqa: F401
 from .scoring import (edit_counts, Vocabulary, word_error_counts, error_measures, make_compute_metrics, cp_wer, tcp_wer,  # noqa: F401
-                      pseudo_word_intervals, hungarian)
+                      pseudo_word_intervals, hungarian, orc_counts, orc_wer, tcorc_wer, filter_empty_segments, create_vad_mask,
+                      find_group_splits, map_utterance_to_split, merge_streams, create_dummy_seg_list, session_tcorc_wer,
+                      session_orc_wer, session_metrics, aggregate_session_metrics)
 from .optim import DiCoWAdamW, clip_grad_norm_, dicow_optimizer  # noqa: F401
 
 __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalGeneration", "SpeakerCommunicationBlock",
@@ -30,4 +32,6 @@ __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalG
            "EnrollmentBank", "plan_enrollment_mixtures", "mix_enrollments", "enrollment_stno", "EnrollmentMixFrontEnd",
            "ResamplePlan", "resample_plan", "resample_segments", "resample", "read_wav", "load_recording",
            "edit_counts", "Vocabulary", "word_error_counts", "error_measures", "make_compute_metrics", "cp_wer", "tcp_wer",
-           "pseudo_word_intervals", "hungarian"]
+           "pseudo_word_intervals", "hungarian", "orc_counts", "orc_wer", "tcorc_wer", "filter_empty_segments", "create_vad_mask",
+           "find_group_splits", "map_utterance_to_split", "merge_streams", "create_dummy_seg_list", "session_tcorc_wer", "session_orc_wer",
+           "session_metrics", "aggregate_session_metrics"]

@@ -1,4 +1,5 @@
-"""Scoring what was decoded, on the GPU: WER / CER per utterance batch and cpWER / tcpWER per session, over launches of csrc/edit_distance.hip.
+"""Scoring what was decoded, on the GPU: WER / CER per utterance batch and cpWER / tcpWER per session, over launches of csrc/edit_distance.hip;
+ORC-WER / tcORC-WER per session, over csrc/orc_distance.hip.
 
 The last step of the reference's evaluation loop.  It scores utterances with jiwer's ``compute_measures`` + ``cer``
 (src/utils/evaluation.py:32-79) and sessions with meeteval's ``cpwer`` / ``tcpwer`` at a collar of 5 s (src/utils/wer.py:30-38, 89-97).
@@ -12,6 +13,14 @@ Here the words (or characters) become dense int32 ids on the host, every Levensh
   * ``make_compute_metrics``  the ``compute_metrics=`` callable for ``Seq2SeqTrainer`` with the reference's behaviour
   * ``cp_wer`` / ``tcp_wer``  one session: all R x H speaker pairs in one launch, the assignment by a small Hungarian solver on the host
   * ``pseudo_word_intervals`` / ``hungarian``   their two host pieces
+  * ``orc_counts``            the thin wrapper of ``dicow_orc_distance``: flat id buffers + three host tables -> the same five counts per problem
+  * ``orc_wer`` / ``tcorc_wer``   one session, ungrouped: every reference utterance goes to whichever hypothesis stream suits it best
+  * ``session_tcorc_wer``     the reference's recipe around meeteval's ``tcorcwer`` (src/utils/wer.py:41-86): empty segments out, a VAD mask,
+    the session cut at silence into groups, never-overlapping hypothesis speakers merged; ALL groups in one ``dicow_orc_distance`` call
+  * ``filter_empty_segments`` / ``create_vad_mask`` / ``find_group_splits`` / ``map_utterance_to_split`` / ``merge_streams`` /
+    ``create_dummy_seg_list``   that recipe's host pieces (src/utils/wer_utils.py:45-138, src/utils/general.py:102-104), in plain numpy
+  * ``session_orc_wer`` / ``session_metrics`` / ``aggregate_session_metrics``   the reference's score sheet (``calc_wer``,
+    ``aggregate_wer_metrics``) as dicts instead of pandas frames
 
 The kernel's definition is exact: unit costs, and among the alignments with the fewest errors the one with the most hits.  ``errors``,
 ``length`` and every rate that is a function of them (``wer``, ``cer``, ``error_rate``) do not depend on how ties are split.
@@ -24,6 +33,12 @@ Restated from the documentation of jiwer and meeteval and NOT pinned to them (ne
   * meeteval's pseudo-word timing for tcpWER: reference words split their segment's span in proportion to their character counts
     ("character_based"), hypothesis words become the centre points of such spans ("character_based_points"), the collar is added on both
     sides of the hypothesis intervals; here in integer ticks of 1 ms with boundaries floored (``pseudo_word_intervals``).
+  * for ORC-WER / tcORC-WER (meeteval is not installed here, and the reference's wer_utils.py imports it at the top, so neither its
+    helpers nor meeteval could be run against this): that an utterance is one reference segment; the sort orders (utterances and a
+    stream's segments by start time, ties in input order; speakers grouped in order of first appearance for ``merge_streams``); the
+    pseudo-word timing of tcORC-WER, taken to be that of tcpWER; the split of equal-error alignments into S / D / I; the choice among
+    tied assignments; the stream label of a group scored against the dummy segment.  ``errors``, ``length`` and ``error_rate`` depend on
+    none of these except the timing.
 
 No CPU fallback: the ids are scored on the GPU or not at all.
 """
@@ -311,3 +326,252 @@ def tcp_wer(ref_segments, hyp_segments, collar: float = 5.0, device="cuda") -> d
     substituted only if their intervals overlap -- ``pseudo_word_intervals`` in ticks of 1 ms, reference words as spans, hypothesis words
     as centre points widened by ``collar`` seconds on both sides."""
     return _session_wer(ref_segments, hyp_segments, True, collar, device)
+
+
+# ------------------------------------------------------------------------------------------------ sessions: ORC-WER and tcORC-WER
+
+def orc_counts(ref_ids: torch.Tensor, hyp_ids: torch.Tensor, problems, utts, streams, ref_iv: Optional[torch.Tensor] = None,
+               hyp_iv: Optional[torch.Tensor] = None, want_assignment: bool = False, out: Optional[torch.Tensor] = None):
+    """One ``dicow_orc_distance`` call.  ``ref_ids`` / ``hyp_ids`` / ``ref_iv`` / ``hyp_iv``: as for ``edit_counts``.  Host tables (int64):
+    ``problems`` ``[n, 4]`` rows ``(utt_first, n_utts, stream_first, n_streams)``; ``utts`` ``[.., 2]`` rows ``(ref_start, ref_len)``, one
+    reference utterance each, in spoken order; ``streams`` ``[.., 2]`` rows ``(hyp_start, hyp_len)``.  Returns int64 ``[n, 5]`` on the
+    CPU, ``(errors, hits, substitutions, deletions, insertions)`` per problem; with ``want_assignment`` also an int32 tensor with one
+    entry per row of ``utts``: the stream within its problem the utterance was given to (-1: the problem has no stream, or no problem
+    names the row).  ``out``: a contiguous int32 ``[n, 2]`` device tensor to receive ``(errors, hits)``."""
+    for t, name in ((ref_ids, "ref_ids"), (hyp_ids, "hyp_ids")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise L.DicowError(f"orc_counts: {name} must be on the GPU (no CPU fallback)")
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise L.DicowError(f"orc_counts: {name} must be a flat contiguous int32 tensor")
+    if hyp_ids.device != ref_ids.device:
+        raise L.DicowError("orc_counts: ref_ids and hyp_ids are on different devices")
+    if (ref_iv is None) != (hyp_iv is None):
+        raise L.DicowError("orc_counts: intervals must be given for both sides or for neither")
+    for iv, ids, name in ((ref_iv, ref_ids, "ref_iv"), (hyp_iv, hyp_ids, "hyp_iv")):
+        if iv is not None and (not torch.is_tensor(iv) or iv.device != ids.device or iv.dtype != torch.int32 or tuple(iv.shape) != (ids.numel(), 2)
+                               or not iv.is_contiguous()):
+            raise L.DicowError(f"orc_counts: {name} must be a contiguous int32 [{ids.numel()}, 2] tensor on {ids.device}")
+    pt = np.ascontiguousarray(np.asarray(problems, dtype=np.int64).reshape(-1, 4))
+    ut = np.ascontiguousarray(np.asarray(utts, dtype=np.int64).reshape(-1, 2))
+    st = np.ascontiguousarray(np.asarray(streams, dtype=np.int64).reshape(-1, 2))
+    n = pt.shape[0]
+    if n and (pt.min() < 0 or (pt[:, 0] + pt[:, 1]).max() > len(ut) or (pt[:, 2] + pt[:, 3]).max() > len(st)):
+        raise L.DicowError("orc_counts: a problem names rows outside the utterance or stream table")
+    dev = ref_ids.device
+    if out is None:
+        out = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.int32 or tuple(out.shape) != (n, 2) or out.device != dev or not out.is_contiguous():
+        raise L.DicowError(f"orc_counts: out must be a contiguous int32 [{n}, 2] tensor on {dev}")
+    asg = torch.full((max(len(ut), 1),), -1, dtype=torch.int32, device=dev) if want_assignment else None
+    tables = (pt.ctypes.data if n else None, n, ut.ctypes.data if len(ut) else None, st.ctypes.data if len(st) else None)
+    with torch.cuda.device(dev):
+        nbytes = L.lib().dicow_orc_distance_ws_bytes(*tables, int(bool(want_assignment)))
+        if nbytes < 0:
+            raise L.DicowError(f"orc_counts: {L.lib().dicow_last_error().decode()}")
+        ws = ops.workspace(nbytes, dev)
+        L.call("dicow_orc_distance", ref_ids.data_ptr(), ref_ids.numel(), hyp_ids.data_ptr(), hyp_ids.numel(), L.ptr(ref_iv), L.ptr(hyp_iv),
+               *tables, out.data_ptr(), L.ptr(asg), ws.data_ptr(), nbytes, L.stream())
+    n_ref = [int(ut[r[0]:r[0] + r[1], 1].sum()) for r in pt]
+    n_hyp = [int(st[r[2]:r[2] + r[3], 1].sum()) for r in pt]
+    counts = counts_from(out.cpu(), np.array([(0, a, 0, b) for a, b in zip(n_ref, n_hyp)], np.int64).reshape(-1, 4))
+    return (counts, asg.cpu()[:len(ut)]) if want_assignment else counts
+
+
+def _relabelled(seg, speaker):
+    """A copy of the segment with another speaker, in the form it came in."""
+    if isinstance(seg, dict):
+        return {**seg, "speaker": speaker}
+    return (speaker,) + tuple(seg[1:])
+
+
+def filter_empty_segments(segments) -> list:
+    """The segments whose text is not the empty string (wer_utils.py:45-46)."""
+    return [seg for seg in segments if _segment(seg)[3] != ""]
+
+
+def create_dummy_seg_list(session_id=None) -> list:
+    """What the reference scores a group without any hypothesis against (general.py:102-104): one segment from 0 s to 0 s of speaker
+    ``''`` with no words."""
+    return [{"session_id": session_id, "start_time": 0, "end_time": 0, "speaker": "", "words": ""}]
+
+
+def create_vad_mask(segments, time_step: float = 0.1, total_duration=None) -> np.ndarray:
+    """Boolean activity per ``time_step`` (wer_utils.py:95-119): ``int(float(total) / time_step) + 1`` frames, total = the latest end
+    unless given; a segment sets frames ``int(float(start) / time_step)`` up to but not including ``int(float(end) / time_step)``."""
+    segs = [_segment(seg) for seg in segments]
+    if total_duration is None:
+        total_duration = max(end for _, _, end, _ in segs)
+    mask = np.zeros(int(float(total_duration) / time_step) + 1, dtype=bool)
+    for _, start, end, _ in segs:
+        mask[int(float(start) / time_step):int(float(end) / time_step)] = 1
+    return mask
+
+
+def find_group_splits(vad, group_duration=30, time_step: float = 0.1) -> list:
+    """The silent frames at which a session is cut (wer_utils.py:122-131): walking the inactive frames in order, the first one at or
+    behind ``group_duration / time_step`` frames after the previous cut (or the start)."""
+    splits = []
+    group_shift = group_duration / time_step
+    next_offset = group_shift
+    for i in np.argwhere(~np.asarray(vad, dtype=bool)).squeeze(axis=-1):
+        if i >= next_offset:
+            splits.append(int(i))
+            next_offset = i + group_shift
+    return splits
+
+
+def map_utterance_to_split(utterance_start_time, splits) -> int:
+    """The group of an utterance (wer_utils.py:134-138): the first split its start time lies strictly before, else ``len(splits)``."""
+    for i, split in enumerate(splits):
+        if utterance_start_time < split:
+            return i
+    return len(splits)
+
+
+def merge_streams(segments) -> list:
+    """Hypothesis speakers that never talk at the same time become one stream (wer_utils.py:63-92): per speaker, in order of first
+    appearance, a VAD mask at 10 ms; the first pair (a, b), a before b in the double loop over that order, whose masks share no frame is
+    merged into a (b's segments relabelled, masks or-ed), and again until no pair is left.  Returns relabelled copies of the segments,
+    sorted by start time."""
+    groups = {}
+    for seg in segments:
+        groups.setdefault(_segment(seg)[0], []).append(seg)
+    masks = {spk: create_vad_mask(segs, time_step=0.01) for spk, segs in groups.items()}
+    longest = max((len(m) for m in masks.values()), default=0)
+    masks = {spk: np.pad(m, (0, longest - len(m))) for spk, m in masks.items()}
+
+    def first_pair():
+        for a in groups:
+            for b in groups:
+                if a != b and not (masks[a] & masks[b]).any():
+                    return a, b
+        return None
+
+    while True:
+        pair = first_pair()
+        if pair is None:
+            break
+        a, b = pair
+        groups[a] = groups[a] + [_relabelled(seg, a) for seg in groups[b]]
+        masks[a] = masks[a] | masks[b]
+        del groups[b], masks[b]
+    return sorted((seg for segs in groups.values() for seg in segs), key=lambda seg: _segment(seg)[1])
+
+
+def _orc_score(groups, timed: bool, collar: float, device) -> dict:
+    """groups: [(reference segments, hypothesis segments)], one ``dicow_orc_distance`` problem each, all in one call."""
+    vocab = Vocabulary()
+    ref_flat, hyp_flat, riv, hiv, utt_rows, stream_rows, problems, labels = [], [], [], [], [], [], [], []
+    for ref, hyp in groups:
+        problems.append([len(utt_rows), 0, len(stream_rows), 0])
+        for _, start, end, text in sorted((_segment(seg) for seg in ref), key=lambda x: x[1]):
+            w = text.split()
+            utt_rows.append((len(ref_flat), len(w)))
+            ref_flat += vocab.ids(w)
+            riv += pseudo_word_intervals(start, end, w, False, 0.0)
+        by = _streams(hyp, True, collar if timed else 0.0)
+        for spk in by:
+            stream_rows.append((len(hyp_flat), len(by[spk][0])))
+            hyp_flat += vocab.ids(by[spk][0])
+            hiv += by[spk][1]
+        labels.append(list(by))
+        problems[-1][1], problems[-1][3] = len(utt_rows) - problems[-1][0], len(stream_rows) - problems[-1][2]
+    timed = timed and bool(ref_flat) and bool(hyp_flat)                     # without words on both sides no two words can be compared
+    rf = torch.tensor(ref_flat, dtype=torch.int32).to(device)
+    hf = torch.tensor(hyp_flat, dtype=torch.int32).to(device)
+    ri = torch.tensor(riv, dtype=torch.int32).reshape(-1, 2).to(device) if timed else None
+    hi = torch.tensor(hiv, dtype=torch.int32).reshape(-1, 2).to(device) if timed else None
+    counts, asg = orc_counts(rf, hf, problems, utt_rows, stream_rows, ri, hi, want_assignment=True)
+    tot = counts.sum(0) if len(problems) else torch.zeros(5, dtype=torch.int64)
+    length = sum(n for _, n in utt_rows)
+    assignment = tuple(labels[g][int(asg[u])] if labels[g] else None for g, p in enumerate(problems) for u in range(p[0], p[0] + p[1]))
+    return {"error_rate": int(tot[0]) / length if length else None, "errors": int(tot[0]), "length": length, "insertions": int(tot[4]),
+            "deletions": int(tot[3]), "substitutions": int(tot[2]), "assignment": assignment}
+
+
+def orc_wer(ref_segments, hyp_segments, device="cuda") -> dict:
+    """Optimal-reference-combination WER of one session, ungrouped (meeteval's ``orcwer``).  Segments as for ``cp_wer``; those without
+    text are dropped.  A reference segment is one utterance, utterances sorted by start time; a hypothesis speaker is one stream as in
+    ``cp_wer``; every utterance goes to the stream that makes the total fewest errors.  Returns ``error_rate errors length insertions
+    deletions substitutions assignment`` (``assignment``: the hypothesis speaker per utterance in sorted order, None without any)."""
+    return _orc_score([(filter_empty_segments(ref_segments), filter_empty_segments(hyp_segments))], False, 0.0, device)
+
+
+def tcorc_wer(ref_segments, hyp_segments, collar: float = 5.0, device="cuda") -> dict:
+    """Time-constrained ORC-WER (meeteval's ``tcorcwer``): as ``orc_wer`` with the word timing and the overlap rule of ``tcp_wer``."""
+    return _orc_score([(filter_empty_segments(ref_segments), filter_empty_segments(hyp_segments))], True, collar, device)
+
+
+def session_tcorc_wer(ref_segments, hyp_segments, collar: float = 5.0, group_duration=5, time_step: float = 0.01, device="cuda") -> dict:
+    """The reference's ``calc_session_tcorc_wer`` with the defaults of its call site (wer.py:41-86, 167-168): segments without text are
+    dropped; the VAD masks of both sides are or-ed; the session is cut at ``find_group_splits``; a segment belongs to the group of its
+    start time; each group's hypothesis -- ``create_dummy_seg_list`` where there is none -- goes through ``merge_streams``; the groups of
+    the reference are scored as tcORC-WER problems, all in ONE ``dicow_orc_distance`` call, their counts summed and their assignments
+    concatenated in group order.  Hypothesis segments of a group without reference are not scored, as in the reference."""
+    ref = filter_empty_segments(ref_segments)
+    hyp = filter_empty_segments(hyp_segments)
+    if not ref:
+        raise ValueError("session_tcorc_wer: no reference segment with text")
+    ref_vad = create_vad_mask(ref, time_step=time_step)
+    hyp_vad = create_vad_mask(hyp, time_step=time_step) if len(hyp) > 0 else ref_vad
+    n = max(len(ref_vad), len(hyp_vad))
+    vad = np.pad(ref_vad, (0, n - len(ref_vad))) | np.pad(hyp_vad, (0, n - len(hyp_vad)))
+    splits = np.array(find_group_splits(vad, group_duration=group_duration, time_step=time_step)) * time_step
+
+    def grouped(segments):
+        out = {}
+        for seg in segments:
+            out.setdefault(map_utterance_to_split(float(_segment(seg)[1]), splits) if len(splits) > 0 else 0, []).append(seg)
+        return out
+
+    ref_groups, hyp_groups = grouped(ref), grouped(hyp)
+    return _orc_score([(ref_groups[g], merge_streams(hyp_groups.get(g, create_dummy_seg_list()))) for g in ref_groups], True, collar, device)
+
+
+def session_orc_wer(ref_segments, hyp_segments, device="cuda") -> dict:
+    """The reference's ``calc_session_orc_wer`` (wer.py:100-106): plain ``orc_wer``, no grouping."""
+    return orc_wer(ref_segments, hyp_segments, device)
+
+
+_SESSION_METRICS = ("cp_wer", "tcp_wer", "tcorc_wer", "orc_wer")
+
+
+def _check_metrics(metrics_list, who):
+    for metric in metrics_list:
+        if metric not in _SESSION_METRICS:
+            raise ValueError(f"{who}: unknown metric {metric!r}, expected some of {_SESSION_METRICS}")
+
+
+def session_metrics(ref_segments, hyp_segments, metrics_list, collar: float = 5.0, device="cuda") -> dict:
+    """One session's row of the reference's score sheet (``calc_wer``, wer.py:157-174) as a dict: for each metric named in
+    ``metrics_list`` (``cp_wer tcp_wer tcorc_wer orc_wer``) the keys of its result prefixed ``cp_`` / ``tcp_`` / ``tcorc_`` / ``orc_``,
+    with ``<p>_error_rate`` renamed ``<p>_wer``."""
+    _check_metrics(metrics_list, "session_metrics")
+    out = {}
+    for metric, fn in (("cp_wer", lambda: cp_wer(ref_segments, hyp_segments, device)),
+                       ("tcp_wer", lambda: tcp_wer(ref_segments, hyp_segments, collar, device)),
+                       ("tcorc_wer", lambda: session_tcorc_wer(ref_segments, hyp_segments, collar, 5, 0.01, device)),
+                       ("orc_wer", lambda: session_orc_wer(ref_segments, hyp_segments, device))):
+        if metric in metrics_list:
+            prefix = metric.split("_", maxsplit=1)[0]
+            for k, v in fn().items():
+                out[f"{prefix}_wer" if k == "error_rate" else f"{prefix}_{k}"] = v
+    return out
+
+
+def aggregate_session_metrics(session_dicts, metrics_list) -> dict:
+    """The reference's ``aggregate_wer_metrics`` (wer_utils.py:167-182) over ``session_metrics`` dicts: every numeric column summed; then
+    per metric named ``<p>_wer = <p>_errors / <p>_length`` and ``<p>_missed_speaker`` / ``_falarm_speaker`` / ``_scored_speaker``, where
+    present, replaced by their means ``<p>_mean_...`` over the sessions."""
+    _check_metrics(metrics_list, "aggregate_session_metrics")
+    rows = list(session_dicts)
+    numeric = [k for k in (rows[0] if rows else {})
+               if all(isinstance(r.get(k), (int, float, np.integer, np.floating)) and not isinstance(r.get(k), bool) for r in rows)]
+    out = {k: sum(r[k] for r in rows) for k in numeric}
+    for metric in metrics_list:
+        prefix = metric.split("_", maxsplit=1)[0]
+        out[f"{prefix}_wer"] = out[f"{prefix}_errors"] / out[f"{prefix}_length"]
+        for k in ("missed_speaker", "falarm_speaker", "scored_speaker"):
+            if f"{prefix}_{k}" in out:
+                out[f"{prefix}_mean_{k}"] = out.pop(f"{prefix}_{k}") / len(rows)
+    return out
