@@ -635,6 +635,53 @@ int dicow_orc_distance(const int32_t* ref_ids, int64_t n_ref, const int32_t* hyp
                        const int64_t* problems, int n_problems, const int64_t* utts, const int64_t* streams, int32_t* out, int32_t* assignment,
                        void* ws, int64_t ws_bytes, void* stream);
 
+/* Scoring diarizations (ABI 7, additive): everything the diarization error rate, the Jaccard error rate and the optimal speaker mapping
+ * are made of, for a batch of independent problems -- one problem is one (reference, hypothesis) pair at one collar -- in exact int64
+ * arithmetic on ticks (samples), without a per-sample mask.  A problem has two tables of the diarization front end (bounds int64 [E + 1]
+ * strictly increasing, active uint64 [E], bit s = speaker s < S <= 64 talks on [bounds[e], bounds[e + 1]); E == 0 is an empty table whose
+ * one bound is not read), a sorted list of disjoint half-open UNSCORED intervals [u0, u1) (they may touch), and a skip_overlap flag.
+ * All tables are HOST memory (checked in full, then copied into the workspace with the stream from where they are: they stay valid until
+ * the stream has made the copies, which for pageable memory is when the call returns), concatenated: bounds int64 [n_bounds], active uint64 [n_active], unscored int64 [n_unscored][2], and
+ * problems int64 [n_problems][DICOW_DIAR_SCORE_ROW] =
+ *   (ref_bounds_first, ref_active_first, Er, Sr, hyp_bounds_first, hyp_active_first, Eh, Sh, unscored_first, n_unscored, skip_overlap, 0):
+ *   the reference's bounds are bounds[ref_bounds_first .. + Er], its bitmasks active[ref_active_first .. + Er - 1], and so on.
+ * The elementary regions of a problem are the intervals between neighbours of the merge of its three endpoint lists; on a region the two
+ * bitmasks are constant: n_ref and n_hyp are their popcounts.  A region is SCORED when it lies in no unscored interval and, with
+ * skip_overlap, n_ref <= 1.  out: device int64 [n_problems][DICOW_DIAR_SCORE_OUT_WORDS], per problem
+ *   [0, 4096)     C[i][j] at i * 64 + j: the scored ticks on which reference speaker i and hypothesis speaker j are both active,
+ *   [4096, 4160)  R[i], [4160, 4224)  H[j]: the scored ticks of each speaker,
+ *   [4224, 4232)  scored (the scored ticks between the first and the last bound of the two tables), total = sum dur * n_ref,
+ *                 missed = sum dur * max(0, n_ref - n_hyp), false_alarm = sum dur * max(0, n_hyp - n_ref), matched = sum dur * min(n_ref,
+ *                 n_hyp), then three zeros.  Every word is written, those of speakers >= S with 0.
+ * Launches: one in which every endpoint finds its rank in the merge by two binary searches in the other lists (ties: reference before
+ * hypothesis before unscored, then by index -- a permutation, so one writer per merged word); one in which a workgroup of 256 threads
+ * stages (dur, ref bits, hyp bits) of `chunk` consecutive regions in LDS (dur = 0 for a region that is not scored) and walks them, every
+ * thread owning 16 fixed cells of C, one wave R and one H, the scalars summed while staging, and writes the chunk's partial sums; one that
+ * adds the partials of every problem in ascending chunk order.  No atomics, one writer per word, nothing read back by the host
+ * (capturable); integer sums, so the result does not depend on the chunk, the grid or the other problems of the call.
+ * chunk: regions per workgroup, 1 .. DICOW_DIAR_SCORE_CHUNK, or 0 for DICOW_DIAR_SCORE_CHUNK.
+ * ws: dicow_diar_score_ws_bytes(...) bytes, 8-byte aligned, at most DICOW_DIAR_SCORE_MAX_WS_BYTES.  With M = the endpoints of a problem
+ * ((Er + 1 if Er else 0) + (Eh + 1 if Eh else 0) + 2 n_unscored) and n_chunks = ceil(max(M - 1, 0) / chunk):
+ *   n_problems * DICOW_DIAR_SCORE_DESC_BYTES + 8 * (n_bounds + n_active + 2 * n_unscored)
+ *   + sum over the problems of 8 * M + 8 * n_chunks * (64 * Sr + 136).
+ * Checked on the host before anything is launched (-1, dicow_last_error() says what): row ranges inside the arrays; 0 <= S <= 64;
+ * E <= DICOW_DIAR_SCORE_MAX_E and n_unscored <= DICOW_DIAR_SCORE_MAX_E per problem; bounds strictly increasing; no speaker bit at or above
+ * S; unscored intervals non-empty, sorted and disjoint; every position in [0, DICOW_DIAR_SCORE_MAX_TICK]; the workspace limit; pointers and
+ * their alignment; ws_bytes.  dicow_diar_score_ws_bytes makes the same checks of the tables and returns -1 where the call would refuse
+ * them.  n_problems == 0 launches nothing. */
+#define DICOW_DIAR_SCORE_CHUNK 256
+#define DICOW_DIAR_SCORE_ROW 12
+#define DICOW_DIAR_SCORE_OUT_WORDS 4232
+#define DICOW_DIAR_SCORE_DESC_BYTES 120
+#define DICOW_DIAR_SCORE_MAX_E 16777216
+#define DICOW_DIAR_SCORE_MAX_TICK 1099511627776LL
+#define DICOW_DIAR_SCORE_MAX_WS_BYTES 4294967296LL
+int64_t dicow_diar_score_ws_bytes(const int64_t* bounds, int64_t n_bounds, const uint64_t* active, int64_t n_active, const int64_t* unscored,
+                                  int64_t n_unscored, const int64_t* problems, int n_problems, int chunk);
+int dicow_diar_score(const int64_t* bounds, int64_t n_bounds, const uint64_t* active, int64_t n_active, const int64_t* unscored,
+                     int64_t n_unscored, const int64_t* problems, int n_problems, int chunk, int64_t* out, void* ws, int64_t ws_bytes,
+                     void* stream);
+
 /* ------------------------------------------------------------------------------------------------ batch augmentation
  * The collator's training-time augmentations (reference src/data/collators.py:189-214), applied to the batch where it
  * already lives (HBM).  The random decisions are drawn on the host from the torch CPU generator in the reference's

@@ -23,6 +23,9 @@ from .scoring import (edit_counts, Vocabulary, word_error_counts, error_measures
                       pseudo_word_intervals, hungarian, orc_counts, orc_wer, tcorc_wer, filter_empty_segments, create_vad_mask,
                       find_group_splits, map_utterance_to_split, merge_streams, create_dummy_seg_list, session_tcorc_wer,
                       session_orc_wer, session_metrics, aggregate_session_metrics)
+from .diar_scoring import (unscored_intervals, diar_score_counts, split_counts, mapping_from_counts, error_from_counts,  # noqa: F401
+                           jaccard_from_counts, aggregate_diarization_scores, diarization_error, jaccard_error, optimal_mapping,
+                           score_diarizations)
 from .optim import DiCoWAdamW, clip_grad_norm_, dicow_optimizer  # noqa: F401
 
 __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalGeneration", "SpeakerCommunicationBlock",
@@ -34,4 +37,6 @@ __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalG
            "edit_counts", "Vocabulary", "word_error_counts", "error_measures", "make_compute_metrics", "cp_wer", "tcp_wer",
            "pseudo_word_intervals", "hungarian", "orc_counts", "orc_wer", "tcorc_wer", "filter_empty_segments", "create_vad_mask",
            "find_group_splits", "map_utterance_to_split", "merge_streams", "create_dummy_seg_list", "session_tcorc_wer", "session_orc_wer",
-           "session_metrics", "aggregate_session_metrics"]
+           "session_metrics", "aggregate_session_metrics", "unscored_intervals", "diar_score_counts", "split_counts", "mapping_from_counts",
+           "error_from_counts", "jaccard_from_counts", "aggregate_diarization_scores", "diarization_error", "jaccard_error", "optimal_mapping",
+           "score_diarizations"]

@@ -82,6 +82,10 @@ EDIT_MAX_LEN, EDIT_K, EDIT_LANES, EDIT_LANES_NARROW = 65535, 8, 512, 64   # DICO
 # DICOW_ORC_*: dicow_orc_distance's limits, chunk and descriptor sizes
 ORC_MAX_STREAMS, ORC_K, ORC_MAX_WORDS, ORC_MAX_STATES, ORC_MAX_WS_BYTES, ORC_DESC_BYTES, ORC_UTT_BYTES = 8, 8, 65527, 1 << 22, 1 << 30, 288, 16
 
+# DICOW_DIAR_SCORE_*: dicow_diar_score's chunk, problem row, output row, descriptor size and limits
+DIAR_SCORE_CHUNK, DIAR_SCORE_ROW, DIAR_SCORE_OUT_WORDS, DIAR_SCORE_DESC_BYTES = 256, 12, 4232, 120
+DIAR_SCORE_MAX_E, DIAR_SCORE_MAX_TICK, DIAR_SCORE_MAX_WS_BYTES = 1 << 24, 1 << 40, 1 << 32
+
 LORA_MAX_R, LORA_MAX_SEG = 192, 24
 LORA_BLOCK, LORA_OUT_F32, LORA_GELU, LORA_MUL_AUX = 1, 2, 4, 8
 
@@ -205,6 +209,7 @@ _SIGS = {
     "dicow_resample": [c_vp, c_i, c_i, c_i, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_i, c_i, c_vp, c_i64, c_vp],
     "dicow_edit_distance": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_i, c_vp, c_i64, c_vp],
     "dicow_orc_distance": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "dicow_diar_score": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_vp, c_vp, c_i64, c_vp],
     "dicow_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
     "dicow_fabric_emulate": [c_vp, c_i64, c_d, c_i, c_i, c_vp],
     "dicow_adamw_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_i, c_vp, c_f, c_vp],
@@ -290,6 +295,7 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
     "dicow_resample_ws_bytes": [c_i, c_i],
     "dicow_edit_distance_ws_bytes": [c_vp, c_i],
     "dicow_orc_distance_ws_bytes": [c_vp, c_i, c_vp, c_vp, c_i],
+    "dicow_diar_score_ws_bytes": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i],
 }
 
 

@@ -117,6 +117,35 @@ class SpeakerSegments:
     def target_indices(self, targets=None):
         return list(range(self.S)) if targets is None else [self.index_of(t) for t in targets]
 
+    def relabelled(self, mapping, default="-1"):
+        """The same diarization under other names, as ``apply_speaker_mapping`` of the reference's
+        ``utils/align_and_compute_der_between_cutsets.py`` renames a hypothesis: speaker ``k`` becomes ``mapping[k]``, a speaker the mapping
+        does not name becomes ``default``.  Speakers that end up under one name are merged: their intervals, sorted, with overlapping and
+        touching ones joined (a union)."""
+        merged, sources = {}, {}
+        for spk in self.speakers:
+            name = mapping.get(spk, default)
+            merged.setdefault(name, []).extend(self.intervals[spk])
+            sources[name] = sources.get(name, 0) + 1
+        for name, iv in merged.items():
+            if sources[name] > 1:
+                out = []
+                for a, b in sorted(iv):
+                    if out and a <= out[-1][1]:
+                        out[-1] = (out[-1][0], max(out[-1][1], b))
+                    else:
+                        out.append((a, b))
+                merged[name] = out
+        return SpeakerSegments(merged, self.n_samples)
+
+    def to_rttm(self, path, recording_id, channel=1):
+        """The inverse of ``from_rttm``: one ``SPEAKER`` line per raw interval, sorted by start, times in seconds with six decimals -- under
+        a hundredth of a sample, so ``from_rttm(path, recording_id, n_samples)`` gives these intervals back exactly."""
+        rows = sorted((a, b, spk) for spk in self.speakers for a, b in self.intervals[spk])
+        with open(path, "w") as f:
+            for a, b, spk in rows:
+                f.write(f"SPEAKER {recording_id} {channel} {a / 16000:.6f} {(b - a) / 16000:.6f} <NA> <NA> {spk} <NA> <NA>\n")
+
 
 def _sweep(per_speaker):
     """One sweep over all interval endpoints, sorted: a running count of open intervals per speaker (a speaker's intervals may overlap), read
