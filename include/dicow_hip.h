@@ -422,7 +422,8 @@ int dicow_ctc_loss_bwd(const dicow_ctc_args* a, const float* grad_scale, void* s
 /* ------------------------------------------------------------------------------------------------ decoder embedding
  * h[b,l,:] = embed_tokens[ids[b,l]] + embed_positions[l]   (HF:modeling_whisper.py:737,754-762), fp32.     */
 int dicow_embed_fwd(const int64_t* ids, const float* tok, const float* pos, float* out, int B, int Lq, int D, void* stream);
-/* d_tok[ids] += g (atomics), d_pos[l] += sum_b g[b,l]; either output may be NULL (frozen). */
+/* d_tok[id] += sum of the rows g[b,l] with ids[b,l] == id, added up in row order; d_pos[l] += sum_b g[b,l] in batch order: no atomics,
+ * two runs give the same bits.  Either output may be NULL (frozen). */
 int dicow_embed_bwd(const int64_t* ids, const float* g, float* d_tok, float* d_pos, int B, int Lq, int D, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ conv-stem backward helpers

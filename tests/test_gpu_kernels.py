@@ -606,6 +606,11 @@ def test_logmel_vs_reference_golden(ops):
     padded, am = features.pad_to_30s(w2)
     out = features.log_mel(padded.cuda(), 80)
     assert out.shape == (2, 80, 6000) and torch.isfinite(out).all()
+    # row by row against the fp64 oracle: the maximum behind the -8 floor is per clip (blockmax[b * gridDim.x + blockIdx.x])
+    from oracle.logmel import log_mel as oracle_log_mel
+    for b in range(2):
+        ref = torch.from_numpy(oracle_log_mel(padded[b].numpy(), 80, dtype=np.float64))
+        assert maxdiff(out[b].cpu(), ref) < 3e-4, (b, maxdiff(out[b].cpu(), ref))
 
 
 @pytest.mark.parametrize("B,H,Lk", [(2, 3, 1), (16, 20, 448), (3, 2, 1500)])

@@ -393,23 +393,52 @@ extern "C" int dicow_embed_fwd(const int64_t* ids, const float* tok, const float
     return DICOW_OK;
 }
 
-__global__ void embed_bwd_kernel(const int64_t* __restrict__ ids, const float* __restrict__ g, float* __restrict__ d_tok,
-                                 float* __restrict__ d_pos, int Lq, int D) {
-    const int row = blockIdx.x;
+// Deterministic, no float atomics: the tied LM head has already accumulated into d_tok when this runs, so atomics in arrival order
+// rounded (base + g_a) + g_b or (base + g_b) + g_a by chance wherever a token occurs twice in the batch -- every batch does (the start
+// token of each row) -- and two runs of one step differed in the last bit.  Instead the FIRST row that holds a token owns it: its
+// workgroup adds the later rows with the same id in row order (the ids are scanned 256 rows at a time; a chunk with a match is walked
+// in order) and adds the sum to d_tok once.  Likewise row l of batch 0 owns position l and adds the batches in order.
+__global__ void __launch_bounds__(256) embed_bwd_kernel(const int64_t* __restrict__ ids, const float* __restrict__ g,
+                                                        float* __restrict__ d_tok, float* __restrict__ d_pos, int rows, int Lq, int D) {
+    __shared__ unsigned char hit[256];
+    const int row = blockIdx.x, tid = threadIdx.x;
     const int l = row % Lq;
     const int64_t id = ids[row];
-    const float* gr = g + (int64_t)row * D;
-    for (int i = threadIdx.x; i < D; i += blockDim.x) {
-        const float v = gr[i];
-        if (d_tok) atomicAdd(d_tok + id * D + i, v);
-        if (d_pos) atomicAdd(d_pos + (int64_t)l * D + i, v);
+    bool owner = d_tok != nullptr;
+    for (int c = 0; owner && c < row; c += 256) {                       // (every condition here is uniform over the workgroup)
+        const int r = c + tid;
+        if (__syncthreads_or(r < row && ids[r] == id)) owner = false;
+    }
+    if (owner) {
+        for (int i0 = 0; i0 < D; i0 += 256) {
+            const int i = i0 + tid;
+            float s = i < D ? g[(int64_t)row * D + i] : 0.f;
+            for (int c = row + 1; c < rows; c += 256) {
+                const int r = c + tid;
+                const bool m = r < rows && ids[r] == id;
+                if (!__syncthreads_or(m)) continue;
+                hit[tid] = m;
+                __syncthreads();
+                if (i < D)
+                    for (int k = 0; k < 256; ++k) if (hit[k]) s += g[(int64_t)(c + k) * D + i];
+                __syncthreads();
+            }
+            if (i < D) d_tok[id * D + i] += s;
+        }
+    }
+    if (d_pos && row < Lq) {
+        for (int i = tid; i < D; i += 256) {
+            float s = g[(int64_t)row * D + i];
+            for (int r = row + Lq; r < rows; r += Lq) s += g[(int64_t)r * D + i];
+            d_pos[(int64_t)l * D + i] += s;
+        }
     }
 }
 
 extern "C" int dicow_embed_bwd(const int64_t* ids, const float* g, float* d_tok, float* d_pos, int B, int Lq, int D, void* stream) {
     DICOW_REQUIRE(ids && g && B > 0 && Lq > 0 && D > 0, "embed_bwd: bad args");
     if (!d_tok && !d_pos) return DICOW_OK;
-    hipLaunchKernelGGL(embed_bwd_kernel, dim3(B * Lq), dim3(256), 0, (hipStream_t)stream, ids, g, d_tok, d_pos, Lq, D);
+    hipLaunchKernelGGL(embed_bwd_kernel, dim3(B * Lq), dim3(256), 0, (hipStream_t)stream, ids, g, d_tok, d_pos, B * Lq, Lq, D);
     DICOW_CHECK_LAUNCH("embed_bwd");
     return DICOW_OK;
 }
