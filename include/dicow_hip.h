@@ -596,6 +596,38 @@ int64_t dicow_edit_distance_ws_bytes(const int64_t* pairs, int n_pairs);
 int dicow_edit_distance(const int32_t* ref_ids, int64_t n_ref, const int32_t* hyp_ids, int64_t n_hyp, const int32_t* ref_iv, const int32_t* hyp_iv,
                         const int64_t* pairs, int n_pairs, int32_t* out, int lanes, int along, void* ws, int64_t ws_bytes, void* stream);
 
+/* Word-level alignments (ABI 7, additive): the edit path behind the counts of dicow_edit_distance -- what jiwer's process_words(...)
+ * .alignments and meeteval's tcp alignment view (the reference's calc_wer(save_visualizations=True), src/utils/wer.py:18-27, 154-155) show.
+ * ref_ids / hyp_ids / ref_iv / hyp_iv / pairs / lanes / along / stream: exactly as for dicow_edit_distance.  Outputs, all device buffers:
+ *   out    int32 [n_pairs][2] = (errors, hits), the values dicow_edit_distance gives;
+ *   ops    uint8, one byte per step of the path: 0 hit, 1 substitution, 2 deletion (a reference word without partner), 3 insertion (a
+ *          hypothesis word without partner).  Pair p owns the slot of ref_len_p + hyp_len_p bytes that starts at the sum of the earlier
+ *          pairs' slot sizes; its path stands in forward order (first word first) at the END of the slot;
+ *   spans  int64 [n_pairs][2] = (first, length): the index in ops of the pair's first op, and the number of ops.
+ *   Nothing in ops outside [first, first + length) is written.
+ * The path is defined on ref and hyp and does not depend on lanes, along or the other pairs: with D[i][j] the key of dicow_edit_distance for
+ * the first i reference and j hypothesis words, from (N_ref, N_hyp) each cell takes the first of these that attains D[i][j]: the diagonal
+ * step (only where rb < he && hb < re, or without intervals; a hit if the ids are equal, -1, otherwise a substitution, + 2^15 or 2^32), a
+ * deletion from D[i-1][j], an insertion from D[i][j-1].  On row or column 0 one step is open; a length of 0 gives all insertions or all
+ * deletions, (0, 0) gives length 0.
+ * Launches: the kernel of dicow_edit_distance compiled with recording -- 2 bits per cell, one 16-bit word per lane per row of its strip,
+ * stored skewed as the lanes produce them, [panel][step][lane], so a step's store is one coalesced row -- and a walk, one wave per pair,
+ * that stages blocks of 128 steps x 64 strips of records in LDS, lets one lane follow the path inside the block and flushes the ops in
+ * coalesced chunks.  No atomics, no waiting between workgroups, one writer per byte, capturable like dicow_edit_distance (one copy, two
+ * launches).  ws: dicow_edit_alignment_ws_bytes(pairs, n_pairs, lanes, along) bytes, 8-byte aligned, at most DICOW_ALIGN_MAX_WS_BYTES: the
+ * two tables (DICOW_ALIGN_TABLE_BYTES a pair), the boundary columns of dicow_edit_distance, and per pair with both lengths > 0, with m the
+ * length along the lanes, n the other, P = lanes * DICOW_EDIT_K, q = ceil(m / P) and w = ceil((m - (q - 1) P) / DICOW_EDIT_K), the records:
+ * 2 * ((q - 1) (n + lanes - 1) lanes + (n + w - 1) w) bytes rounded up to 8.
+ * Checked on the host before anything is launched (-1, dicow_last_error()): everything dicow_edit_distance checks; the workspace limit;
+ * out / ops / spans non-null, spans 8-byte aligned; ws_bytes.  dicow_edit_alignment_ws_bytes returns -1 for a table, lanes or along the
+ * call would refuse.  n_pairs == 0 launches nothing. */
+#define DICOW_ALIGN_MAX_WS_BYTES 1073741824LL
+#define DICOW_ALIGN_TABLE_BYTES 56
+int64_t dicow_edit_alignment_ws_bytes(const int64_t* pairs, int n_pairs, int lanes, int along);
+int dicow_edit_alignment(const int32_t* ref_ids, int64_t n_ref, const int32_t* hyp_ids, int64_t n_hyp, const int32_t* ref_iv, const int32_t* hyp_iv,
+                         const int64_t* pairs, int n_pairs, int32_t* out, uint8_t* ops, int64_t* spans, int lanes, int along, void* ws,
+                         int64_t ws_bytes, void* stream);
+
 /* Scoring sessions whose speaker labels are not trusted (ABI 7, additive): optimal-reference-combination WER and its time-constrained form
  * (ORC-WER / tcORC-WER; meeteval's orcwer / tcorcwer, which the reference calls per group of a session, src/utils/wer.py:41-106) for a batch
  * of independent problems -- one problem is one group of one session.  ref_ids / hyp_ids / ref_iv / hyp_iv: as for dicow_edit_distance.

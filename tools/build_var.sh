@@ -4,10 +4,24 @@
 # -> tools/libv_<name>.so (git-ignored; travels to the GPU box).  Used with DICOW_HIP_LIB=...   The variant OBJECTS go to gpurun_out/var_build/
 # (never pushed to the GPU box, never in csrc/build/).  attention.hip has one flag left without -DDICOW_EXPERIMENTS: -DATTN_FUSED_PROFILE=1
 # (the variants of the forward kernel need the experiments build: tools/build_attn_variants.sh).
+# Any other source file:  tools/build_var.sh --file edit_alignment.hip name "flags" [name "flags" ...]  -> tools/libv_<name>.so with that one
+# file compiled under the flags and every other object the shipped one.
 set -e
 cd "$(dirname "$0")/../ts-asr-whisper_amd/csrc"
 bash build.sh > /dev/null
 VB=../../gpurun_out/var_build; mkdir -p $VB
+if [ "$1" = "--file" ]; then
+  src=$2; b=${src%.hip}; shift 2
+  while [ $# -gt 1 ]; do
+    n=$1; f=$2; shift 2
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c $src -o $VB/${b}_v_$n.o $f
+    objs=""
+    for s in $(ls *.hip); do if [ "$s" = "$src" ]; then objs="$objs $VB/${b}_v_$n.o"; else objs="$objs build/${s%.hip}.o"; fi; done
+    hipcc --offload-arch=gfx950 -shared -fPIC $objs -o ../../tools/libv_$n.so
+    echo "built tools/libv_$n.so"
+  done
+  exit 0
+fi
 pids=""
 names=()
 while [ $# -gt 4 ]; do

@@ -22,7 +22,8 @@ from .wave_intake import (ResamplePlan, resample_plan, resample_segments, resamp
 from .scoring import (edit_counts, Vocabulary, word_error_counts, error_measures, make_compute_metrics, cp_wer, tcp_wer,  # noqa: F401
                       pseudo_word_intervals, hungarian, orc_counts, orc_wer, tcorc_wer, filter_empty_segments, create_vad_mask,
                       find_group_splits, map_utterance_to_split, merge_streams, create_dummy_seg_list, session_tcorc_wer,
-                      session_orc_wer, session_metrics, aggregate_session_metrics)
+                      session_orc_wer, session_metrics, aggregate_session_metrics, edit_alignments, alignment_chunks, alignment_rows,
+                      word_alignments, format_alignment, session_alignment, error_breakdown, save_alignment_report)
 from .diar_scoring import (unscored_intervals, diar_score_counts, split_counts, mapping_from_counts, error_from_counts,  # noqa: F401
                            jaccard_from_counts, aggregate_diarization_scores, diarization_error, jaccard_error, optimal_mapping,
                            score_diarizations)
@@ -37,6 +38,7 @@ __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalG
            "edit_counts", "Vocabulary", "word_error_counts", "error_measures", "make_compute_metrics", "cp_wer", "tcp_wer",
            "pseudo_word_intervals", "hungarian", "orc_counts", "orc_wer", "tcorc_wer", "filter_empty_segments", "create_vad_mask",
            "find_group_splits", "map_utterance_to_split", "merge_streams", "create_dummy_seg_list", "session_tcorc_wer", "session_orc_wer",
-           "session_metrics", "aggregate_session_metrics", "unscored_intervals", "diar_score_counts", "split_counts", "mapping_from_counts",
+           "session_metrics", "aggregate_session_metrics", "edit_alignments", "alignment_chunks", "alignment_rows", "word_alignments",
+           "format_alignment", "session_alignment", "error_breakdown", "save_alignment_report", "unscored_intervals", "diar_score_counts", "split_counts", "mapping_from_counts",
            "error_from_counts", "jaccard_from_counts", "aggregate_diarization_scores", "diarization_error", "jaccard_error", "optimal_mapping",
            "score_diarizations"]

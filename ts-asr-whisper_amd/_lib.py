@@ -79,6 +79,8 @@ RESAMPLE_LDS_BYTES, RESAMPLE_MAX_RATIO, RESAMPLE_MAX_CHANNELS = 49152, 1 << 20, 
 
 EDIT_MAX_LEN, EDIT_K, EDIT_LANES, EDIT_LANES_NARROW = 65535, 8, 512, 64   # DICOW_EDIT_*: dicow_edit_distance's limit, strip and workgroups
 
+ALIGN_MAX_WS_BYTES, ALIGN_TABLE_BYTES = 1 << 30, 56   # DICOW_ALIGN_*: dicow_edit_alignment's workspace limit and its tables' bytes per pair
+
 # DICOW_ORC_*: dicow_orc_distance's limits, chunk and descriptor sizes
 ORC_MAX_STREAMS, ORC_K, ORC_MAX_WORDS, ORC_MAX_STATES, ORC_MAX_WS_BYTES, ORC_DESC_BYTES, ORC_UTT_BYTES = 8, 8, 65527, 1 << 22, 1 << 30, 288, 16
 
@@ -208,6 +210,7 @@ _SIGS = {
     "dicow_enrollment_mix": [c_vp, c_i64, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_vp],
     "dicow_resample": [c_vp, c_i, c_i, c_i, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_i, c_i, c_vp, c_i64, c_vp],
     "dicow_edit_distance": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_i, c_vp, c_i64, c_vp],
+    "dicow_edit_alignment": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_i, c_i, c_vp, c_i64, c_vp],
     "dicow_orc_distance": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "dicow_diar_score": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_vp, c_vp, c_i64, c_vp],
     "dicow_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
@@ -294,6 +297,7 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
     "dicow_enrollment_windows_ws_bytes": [c_i64, c_i],
     "dicow_resample_ws_bytes": [c_i, c_i],
     "dicow_edit_distance_ws_bytes": [c_vp, c_i],
+    "dicow_edit_alignment_ws_bytes": [c_vp, c_i, c_i, c_i],
     "dicow_orc_distance_ws_bytes": [c_vp, c_i, c_vp, c_vp, c_i],
     "dicow_diar_score_ws_bytes": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i],
 }

@@ -18,165 +18,8 @@
 // LANES at a time to the pair's slice of the workspace, two columns per pair by panel parity: one writer per slot, no atomics.  Columns
 // behind m in the last panel are computed like the others (symbol 0, row-0 key clamped at m) and never read: values flow left to right.
 // The lane that owns column m holds D[n][m] after the last panel and writes (E, H).
-#include "common.h"
-#include <algorithm>
-#include <vector>
-
-#define ED_K DICOW_EDIT_K
-#define ED_WIDE DICOW_EDIT_LANES
-#define ED_NARROW DICOW_EDIT_LANES_NARROW
-#define ED_I32_MAX_SUM (65535 - ED_WIDE * ED_K)
-
-struct ed_pair { int64_t col_start, row_start, bnd_off; int32_t m, n, cols_hyp, pad; };      // bnd_off: bytes from ws to the pair's [2][n] keys
-
-struct ed_args {
-    const int32_t* ref_ids;
-    const int32_t* hyp_ids;
-    const int32_t* ref_iv;
-    const int32_t* hyp_iv;
-    const ed_pair* pairs;
-    char* ws;
-    int32_t* out;
-};
-
-template <typename KEY> struct ed_unit;
-template <> struct ed_unit<int32_t> { static constexpr int SHIFT = 15; };
-template <> struct ed_unit<int64_t> { static constexpr int SHIFT = 32; };
-
-// what flows from lane to lane: the key right of a strip, and the row it belongs to
-template <typename KEY, bool IV> struct ed_msg { KEY key; int32_t sym; };
-template <typename KEY> struct ed_msg<KEY, true> { KEY key; int32_t sym, ib, ie; };
-
-template <typename KEY, bool IV, int LANES>
-__global__ void __launch_bounds__(LANES) edit_distance_kernel(const ed_args a) {
-    using MSG = ed_msg<KEY, IV>;
-    constexpr KEY UNIT = (KEY)1 << ed_unit<KEY>::SHIFT;
-    constexpr int P = LANES * ED_K;
-    __shared__ MSG hand[2][LANES];
-    __shared__ MSG stage_in[LANES];
-    __shared__ KEY stage_out[2][LANES];
-    const int t = threadIdx.x;
-    const ed_pair pr = a.pairs[blockIdx.x];
-    const int m = pr.m, n = pr.n;
-    int32_t* out = a.out + 2 * (int64_t)blockIdx.x;
-    if (m == 0 || n == 0) {
-        if (t == 0) { out[0] = m + n; out[1] = 0; }
-        return;
-    }
-    const int32_t* col_ids = (pr.cols_hyp ? a.hyp_ids : a.ref_ids) + pr.col_start;
-    const int32_t* row_ids = (pr.cols_hyp ? a.ref_ids : a.hyp_ids) + pr.row_start;
-    const int32_t* col_iv = nullptr;
-    const int32_t* row_iv = nullptr;
-    if constexpr (IV) {
-        col_iv = (pr.cols_hyp ? a.hyp_iv : a.ref_iv) + 2 * pr.col_start;
-        row_iv = (pr.cols_hyp ? a.ref_iv : a.hyp_iv) + 2 * pr.row_start;
-    }
-    KEY* bnd = reinterpret_cast<KEY*>(a.ws + pr.bnd_off);
-    const int panels = (m + P - 1) / P;
-    const int T = n + LANES - 1;                                               // steps of a panel
-    KEY cur[ED_K];
-    for (int p = 0; p < panels; ++p) {
-        const int j0 = p * P + t * ED_K;                                       // the strip's first column (0-based; D's column j0 + 1)
-        const bool has_in = p > 0, has_out = p + 1 < panels;
-        const KEY* bin = bnd + (size_t)((p + 1) & 1) * n;                      // the previous panel's last column, rows 1 .. n
-        KEY* bout = bnd + (size_t)(p & 1) * n;
-        int32_t asym[ED_K], ab[ED_K], ae[ED_K];
-#pragma unroll
-        for (int k = 0; k < ED_K; ++k) {
-            const int j = j0 + k;
-            cur[k] = (KEY)min(j + 1, m) * UNIT;                                // D[0][j + 1]
-            asym[k] = j < m ? col_ids[j] : 0;
-            if constexpr (IV) {
-                ab[k] = j < m ? col_iv[2 * j] : 0;
-                ae[k] = j < m ? col_iv[2 * j + 1] : 0;
-            }
-        }
-        KEY diag = (KEY)min(j0, m) * UNIT;                                     // D[0][j0]
-        auto load_row = [&](int r) {                                           // lane 0's message for row r (0-based)
-            MSG g;
-            g.key = 0; g.sym = 0;
-            if constexpr (IV) { g.ib = 0; g.ie = 0; }
-            if (r < n) {
-                g.key = has_in ? bin[r] : (KEY)(r + 1) * UNIT;
-                g.sym = row_ids[r];
-                if constexpr (IV) { g.ib = row_iv[2 * r]; g.ie = row_iv[2 * r + 1]; }
-            }
-            return g;
-        };
-        auto flush = [&](int sf) {                                             // the last lane's keys of steps sf .. sf + LANES - 1
-            const int r = sf + t - (LANES - 1);
-            if (r >= 0 && r < n) bout[r] = stage_out[(sf / LANES) & 1][t];
-        };
-        MSG pre = load_row(t);
-        for (int s0 = 0; s0 < T; s0 += LANES) {
-            if (has_out && s0 > 0) flush(s0 - LANES);
-            stage_in[t] = pre;                                                 // read by lane 0 at step s0 + t: behind the barrier of step s0
-            pre = load_row(s0 + LANES + t);
-            const int s1 = min(s0 + LANES, T);
-            for (int s = s0; s < s1; ++s) {
-                const int r = s - t;
-                const MSG in = t == 0 ? stage_in[s - s0] : hand[(s + 1) & 1][t - 1];
-                if (r >= 0 && r < n) {
-                    // v[k] = min(a[k], v[k - 1] + UNIT), a[k] = min(up + UNIT, diagonal step).  With everything of column k lowered
-                    // by k UNIT the chain along the strip is one min per cell; the rest has no dependence from cell to cell.
-                    KEY d = diag, a[ED_K];
-                    diag = in.key;
-#pragma unroll
-                    for (int k = 0; k < ED_K; ++k) {
-                        const KEY up = cur[k];
-                        const KEY c = d + (asym[k] == in.sym ? (KEY)-1 - k * UNIT : UNIT - k * UNIT);
-                        const KEY x = up + (UNIT - k * UNIT);
-                        bool open = true;
-                        if constexpr (IV) open = in.ib < ae[k] && ab[k] < in.ie;
-                        a[k] = open ? min(x, c) : x;
-                        d = up;
-                    }
-                    KEY run = in.key + UNIT;
-#pragma unroll
-                    for (int k = 0; k < ED_K; ++k) {
-                        run = min(run, a[k]);
-                        cur[k] = run + k * UNIT;
-                    }
-                }
-                MSG o = in;
-                o.key = cur[ED_K - 1];
-                hand[s & 1][t] = o;
-                if (has_out && t == LANES - 1) stage_out[(s0 / LANES) & 1][s - s0] = cur[ED_K - 1];
-                __syncthreads();
-            }
-        }
-        if (has_out) flush((T - 1) / LANES * LANES);
-        __syncthreads();                                                       // the column is visible to the next panel's loads
-    }
-    const int q = m - 1 - (panels - 1) * P;                                    // column m in the last panel
-    if (t == q / ED_K) {
-        KEY v = cur[0];
-#pragma unroll
-        for (int k = 1; k < ED_K; ++k) v = (q % ED_K == k) ? cur[k] : v;
-        const KEY e = (v + (UNIT - 1)) >> ed_unit<KEY>::SHIFT;                 // v = E UNIT - H, 0 <= H < UNIT
-        out[0] = (int32_t)e;
-        out[1] = (int32_t)(e * UNIT - v);
-    }
-}
-
-static inline int64_t ed_steps(int64_t m, int64_t n, int lanes) { return (m + (int64_t)lanes * ED_K - 1) / ((int64_t)lanes * ED_K) * (n + lanes - 1); }
-
-static inline int64_t ed_bnd_bytes(int64_t ref_len, int64_t hyp_len) {        // two columns of 8-byte slots when some plan may need a second panel
-    const int64_t longer = std::max(ref_len, hyp_len);
-    return longer > (int64_t)ED_NARROW * ED_K ? 16 * longer : 0;
-}
-
-static int ed_check_lens(const char* who, const int64_t* pairs, int n_pairs) {
-    DICOW_REQUIRE(n_pairs >= 0, "%s: negative n_pairs=%d", who, n_pairs);
-    DICOW_REQUIRE(n_pairs == 0 || pairs, "%s: null pair table", who);
-    for (int k = 0; k < n_pairs; ++k) {
-        const int64_t rl = pairs[4 * (int64_t)k + 1], hl = pairs[4 * (int64_t)k + 3];
-        DICOW_REQUIRE(rl >= 0 && hl >= 0, "%s: pair %d has a negative length (ref_len=%lld, hyp_len=%lld)", who, k, (long long)rl, (long long)hl);
-        DICOW_REQUIRE(rl <= DICOW_EDIT_MAX_LEN && hl <= DICOW_EDIT_MAX_LEN, "%s: pair %d is longer (ref_len=%lld, hyp_len=%lld) than DICOW_EDIT_MAX_LEN = %d",
-                      who, k, (long long)rl, (long long)hl, DICOW_EDIT_MAX_LEN);
-    }
-    return DICOW_OK;
-}
+// The kernel and the host pieces shared with edit_alignment.hip: edit_distance_core.inc (REC = false here).
+#include "edit_distance_core.inc"
 
 extern "C" int64_t dicow_edit_distance_ws_bytes(const int64_t* pairs, int n_pairs) {
     if (ed_check_lens("edit_distance_ws_bytes", pairs, n_pairs) != DICOW_OK) return -1;

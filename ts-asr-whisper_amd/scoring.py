@@ -13,6 +13,13 @@ Here the words (or characters) become dense int32 ids on the host, every Levensh
   * ``make_compute_metrics``  the ``compute_metrics=`` callable for ``Seq2SeqTrainer`` with the reference's behaviour
   * ``cp_wer`` / ``tcp_wer``  one session: all R x H speaker pairs in one launch, the assignment by a small Hungarian solver on the host
   * ``pseudo_word_intervals`` / ``hungarian``   their two host pieces
+  * ``edit_alignments``       the edit path behind ``edit_counts``: ``dicow_edit_alignment`` over the pairs (csrc/edit_alignment.hip), split over
+    several calls when the records would pass the workspace limit -> the counts and one uint8 tensor of ops per pair
+  * ``word_alignments`` / ``alignment_chunks``   per utterance the chunks of jiwer's ``process_words(...).alignments``, with the batch's measures
+  * ``session_alignment``     the data behind the reference's tcp alignment view (``calc_wer(save_visualizations=True)``, src/utils/wer.py:18-27,
+    154-155): the assignment of ``tcp_wer`` / ``cp_wer``, then the assigned pairs aligned in one call, as rows of words and times
+  * ``alignment_rows`` / ``format_alignment`` / ``error_breakdown`` / ``save_alignment_report``   ops against words, a three-line text rendering,
+    the most frequent errors, one JSON file per session -- the project's own layouts
   * ``orc_counts``            the thin wrapper of ``dicow_orc_distance``: flat id buffers + three host tables -> the same five counts per problem
   * ``orc_wer`` / ``tcorc_wer``   one session, ungrouped: every reference utterance goes to whichever hypothesis stream suits it best
   * ``session_tcorc_wer``     the reference's recipe around meeteval's ``tcorcwer`` (src/utils/wer.py:41-86): empty segments out, a VAD mask,
@@ -30,6 +37,9 @@ Restated from the documentation of jiwer and meeteval and NOT pinned to them (ne
     ``wil = 1 - wip``; ``cer`` over the characters of the normalised strings, spaces included;
   * how substitutions / deletions / insertions are split among alignments with the same number of errors (here: most hits first;
     the libraries backtrace one alignment of their own choosing), which moves ``mer`` / ``wip`` / ``wil`` and the three counts, never ``errors``;
+  * which of several paths of equal counts an alignment shows (here: walking back, the diagonal where it attains the key, else the
+    deletion, else the insertion; jiwer / rapidfuzz and meeteval may show another), and the renderings of ``format_alignment`` and
+    ``save_alignment_report``, which are this project's own;
   * meeteval's pseudo-word timing for tcpWER: reference words split their segment's span in proportion to their character counts
     ("character_based"), hypothesis words become the centre points of such spans ("character_based_points"), the collar is added on both
     sides of the hypothesis intervals; here in integer ticks of 1 ms with boundaries floored (``pseudo_word_intervals``).
@@ -55,6 +65,23 @@ TICKS_PER_SECOND = 1000
 _TIMESTAMP = re.compile(r"\<\|\d+\.\d+\|\>")
 
 
+def _check_edit_inputs(who: str, ref_ids, hyp_ids, ref_iv, hyp_iv):
+    """The refusals ``edit_counts`` and ``edit_alignments`` share: flat contiguous int32 ids on one GPU, intervals for both sides or neither."""
+    for t, name in ((ref_ids, "ref_ids"), (hyp_ids, "hyp_ids")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise L.DicowError(f"{who}: {name} must be on the GPU (no CPU fallback)")
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise L.DicowError(f"{who}: {name} must be a flat contiguous int32 tensor")
+    if hyp_ids.device != ref_ids.device:
+        raise L.DicowError(f"{who}: ref_ids and hyp_ids are on different devices")
+    if (ref_iv is None) != (hyp_iv is None):
+        raise L.DicowError(f"{who}: intervals must be given for both sides or for neither")
+    for iv, ids, name in ((ref_iv, ref_ids, "ref_iv"), (hyp_iv, hyp_ids, "hyp_iv")):
+        if iv is not None and (not torch.is_tensor(iv) or iv.device != ids.device or iv.dtype != torch.int32 or tuple(iv.shape) != (ids.numel(), 2)
+                               or not iv.is_contiguous()):
+            raise L.DicowError(f"{who}: {name} must be a contiguous int32 [{ids.numel()}, 2] tensor on {ids.device}")
+
+
 def edit_counts(ref_ids: torch.Tensor, hyp_ids: torch.Tensor, pairs, ref_iv: Optional[torch.Tensor] = None,
                 hyp_iv: Optional[torch.Tensor] = None, lanes: int = 0, along: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One ``dicow_edit_distance`` launch.  ``ref_ids`` / ``hyp_ids``: flat contiguous int32 on the GPU; ``pairs``: int64 ``[n, 4]`` on the
@@ -62,19 +89,7 @@ def edit_counts(ref_ids: torch.Tensor, hyp_ids: torch.Tensor, pairs, ref_iv: Opt
     (begin, end) ticks per id, both or neither.  Returns int64 ``[n, 5]`` on the CPU: ``(errors, hits, substitutions, deletions,
     insertions)``.  ``lanes`` / ``along``: the workgroup width and which sequence lies along the lanes, 0 = the library's choice; the
     result depends on neither.  ``out``: a contiguous int32 ``[n, 2]`` device tensor to receive ``(errors, hits)``."""
-    for t, name in ((ref_ids, "ref_ids"), (hyp_ids, "hyp_ids")):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise L.DicowError(f"edit_counts: {name} must be on the GPU (no CPU fallback)")
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
-            raise L.DicowError(f"edit_counts: {name} must be a flat contiguous int32 tensor")
-    if hyp_ids.device != ref_ids.device:
-        raise L.DicowError("edit_counts: ref_ids and hyp_ids are on different devices")
-    if (ref_iv is None) != (hyp_iv is None):
-        raise L.DicowError("edit_counts: intervals must be given for both sides or for neither")
-    for iv, ids, name in ((ref_iv, ref_ids, "ref_iv"), (hyp_iv, hyp_ids, "hyp_iv")):
-        if iv is not None and (not torch.is_tensor(iv) or iv.device != ids.device or iv.dtype != torch.int32 or tuple(iv.shape) != (ids.numel(), 2)
-                               or not iv.is_contiguous()):
-            raise L.DicowError(f"edit_counts: {name} must be a contiguous int32 [{ids.numel()}, 2] tensor on {ids.device}")
+    _check_edit_inputs("edit_counts", ref_ids, hyp_ids, ref_iv, hyp_iv)
     table = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 4))
     n = table.shape[0]
     if out is None:
@@ -135,20 +150,28 @@ def _flat(streams, device):
     return torch.from_numpy(flat).to(device), starts, np.asarray(lens, np.int64)
 
 
+def _utterance_pairs(who: str, refs, hyps, text_norm, unit: str, device):
+    """Lists of strings -> (flat ref ids, flat hyp ids, the pair table with one row per utterance, ref tokens, hyp tokens)."""
+    refs, hyps = list(refs), list(hyps)
+    if len(refs) != len(hyps):
+        raise ValueError(f"{who}: {len(refs)} references and {len(hyps)} hypotheses")
+    norm = _default_norm if text_norm is None else text_norm
+    vocab = Vocabulary()
+    rt = [_tokens(norm(s), unit) for s in refs]
+    ht = [_tokens(norm(s), unit) for s in hyps]
+    r = [vocab.ids(t) for t in rt]                                           # (all references first, as before: ids are only compared)
+    h = [vocab.ids(t) for t in ht]
+    rf, rs, rl = _flat(r, device)
+    hf, hs, hl = _flat(h, device)
+    return rf, hf, (np.stack([rs, rl, hs, hl], axis=1) if refs else np.zeros((0, 4), np.int64)), rt, ht
+
+
 def word_error_counts(refs, hyps, text_norm: Optional[Callable] = None, unit: str = "word", device="cuda") -> torch.Tensor:
     """Lists of strings, one pair per utterance, one launch -> int64 ``[n, 5]`` ``(errors, hits, substitutions, deletions, insertions)``.
     ``text_norm``: str -> str, applied to both sides (default: lower case, whitespace collapsed); ``unit``: words split at whitespace, or
     the characters of the normalised string."""
-    refs, hyps = list(refs), list(hyps)
-    if len(refs) != len(hyps):
-        raise ValueError(f"word_error_counts: {len(refs)} references and {len(hyps)} hypotheses")
-    norm = _default_norm if text_norm is None else text_norm
-    vocab = Vocabulary()
-    r = [vocab.ids(_tokens(norm(s), unit)) for s in refs]
-    h = [vocab.ids(_tokens(norm(s), unit)) for s in hyps]
-    rf, rs, rl = _flat(r, device)
-    hf, hs, hl = _flat(h, device)
-    return edit_counts(rf, hf, np.stack([rs, rl, hs, hl], axis=1) if refs else np.zeros((0, 4), np.int64))
+    rf, hf, table, _, _ = _utterance_pairs("word_error_counts", refs, hyps, text_norm, unit, device)
+    return edit_counts(rf, hf, table)
 
 
 def measures_from_counts(hits: int, substitutions: int, deletions: int, insertions: int) -> dict:
@@ -282,7 +305,9 @@ def hungarian(cost) -> list:
     return col
 
 
-def _session_wer(ref_segments, hyp_segments, timed: bool, collar: float, device) -> dict:
+def _session_score(ref_segments, hyp_segments, timed: bool, collar: float, device):
+    """(the result of ``cp_wer`` / ``tcp_wer``, what ``session_alignment`` needs to align the assigned pairs: the streams, their flat
+    buffers and the assignment ``col``)."""
     ref = _streams(ref_segments, False, 0.0)
     hyp = _streams(hyp_segments, True, collar)
     rk, hk = list(ref), list(hyp)
@@ -292,9 +317,9 @@ def _session_wer(ref_segments, hyp_segments, timed: bool, collar: float, device)
     hf, hs, hl = _flat([vocab.ids(hyp[k][0]) for k in hk], device)
     n = max(R, H)
     counts = np.zeros((n, n, 5), np.int64)                                  # (E, H, S, D, I); a missing speaker is an empty stream
+    riv = hiv = None
     if R and H:
         table = np.array([(rs[i], rl[i], hs[j], hl[j]) for i in range(R) for j in range(H)], np.int64)
-        riv = hiv = None
         if timed:
             riv = torch.tensor([iv for k in rk for iv in ref[k][1]], dtype=torch.int32).reshape(-1, 2).to(device)
             hiv = torch.tensor([iv for k in hk for iv in hyp[k][1]], dtype=torch.int32).reshape(-1, 2).to(device)
@@ -307,9 +332,14 @@ def _session_wer(ref_segments, hyp_segments, timed: bool, collar: float, device)
     tot = sum((counts[i, col[i]] for i in range(n)), np.zeros(5, np.int64))
     length = int(rl.sum())
     assignment = [(rk[i] if i < R else None, hk[col[i]] if col[i] < H else None) for i in range(n)]
-    return {"error_rate": int(tot[0]) / length if length else None, "errors": int(tot[0]), "length": length, "insertions": int(tot[4]),
-            "deletions": int(tot[3]), "substitutions": int(tot[2]), "missed_speaker": max(0, R - H), "falarm_speaker": max(0, H - R),
-            "scored_speaker": R, "assignment": assignment}
+    result = {"error_rate": int(tot[0]) / length if length else None, "errors": int(tot[0]), "length": length, "insertions": int(tot[4]),
+              "deletions": int(tot[3]), "substitutions": int(tot[2]), "missed_speaker": max(0, R - H), "falarm_speaker": max(0, H - R),
+              "scored_speaker": R, "assignment": assignment}
+    return result, dict(ref=ref, hyp=hyp, rk=rk, hk=hk, rf=rf, hf=hf, rs=rs, rl=rl, hs=hs, hl=hl, riv=riv, hiv=hiv, col=col)
+
+
+def _session_wer(ref_segments, hyp_segments, timed: bool, collar: float, device) -> dict:
+    return _session_score(ref_segments, hyp_segments, timed, collar, device)[0]
 
 
 def cp_wer(ref_segments, hyp_segments, device="cuda") -> dict:
@@ -575,3 +605,176 @@ def aggregate_session_metrics(session_dicts, metrics_list) -> dict:
             if f"{prefix}_{k}" in out:
                 out[f"{prefix}_mean_{k}"] = out.pop(f"{prefix}_{k}") / len(rows)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ word-level alignments
+
+OPS = ("equal", "substitute", "delete", "insert")     # the bytes of dicow_edit_alignment's ops, by jiwer's chunk names
+
+
+def _alignment_call(ref_ids, hyp_ids, table, ref_iv, hyp_iv, lanes, along, nbytes):
+    """One ``dicow_edit_alignment`` call -> ((errors, hits) int32 [n, 2], ops uint8, spans int64 [n, 2]), all on the CPU."""
+    n, dev = table.shape[0], ref_ids.device
+    out = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    path = torch.empty((max(int(table[:, 1].sum() + table[:, 3].sum()), 1),), dtype=torch.uint8, device=dev)
+    spans = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        # the records of a session run to hundreds of MB: past the size of the persistent scratch they are a tensor of this call
+        ws = ops.workspace(nbytes, dev) if nbytes <= (64 << 20) else torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        L.call("dicow_edit_alignment", ref_ids.data_ptr(), ref_ids.numel(), hyp_ids.data_ptr(), hyp_ids.numel(), L.ptr(ref_iv), L.ptr(hyp_iv),
+               table.ctypes.data, n, out.data_ptr(), path.data_ptr(), spans.data_ptr(), int(lanes), int(along), ws.data_ptr(), nbytes, L.stream())
+    return out.cpu(), path.cpu(), spans.cpu()
+
+
+def edit_alignments(ref_ids: torch.Tensor, hyp_ids: torch.Tensor, pairs, ref_iv: Optional[torch.Tensor] = None,
+                    hyp_iv: Optional[torch.Tensor] = None, lanes: int = 0, along: int = 0):
+    """The edit path behind ``edit_counts``, arguments as there: ``dicow_edit_alignment`` over the pairs.  Returns ``(counts, paths)``:
+    ``counts`` int64 ``[n, 5]`` on the CPU, equal to ``edit_counts`` of the same call; ``paths`` a list with one uint8 CPU tensor per pair,
+    one byte per step in forward order, ``0`` hit, ``1`` substitution, ``2`` deletion, ``3`` insertion (``OPS`` names them).  Among paths of
+    the same key the one that, walking back from the end, takes the diagonal where it is open and attains the key, else the deletion, else
+    the insertion.  The kernel keeps 2 bits per cell of every table of a call in its workspace: a pair list whose records pass
+    ``DICOW_ALIGN_MAX_WS_BYTES`` is split over several calls (the result does not depend on the split); a pair that does not fit alone
+    is refused."""
+    _check_edit_inputs("edit_alignments", ref_ids, hyp_ids, ref_iv, hyp_iv)
+    table = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 4))
+    n = table.shape[0]
+    if n == 0:
+        return counts_from(np.zeros((0, 2), np.int32), table), []
+    if lanes == 0 and 0 <= int(table[:, [1, 3]].min()) and int(table[:, [1, 3]].max()) <= L.EDIT_MAX_LEN:
+        # the library's choice for the whole list, fixed here so that a split does not change the plan
+        lanes = L.EDIT_LANES if int(table[:, [1, 3]].min(axis=1).max()) > L.EDIT_LANES_NARROW * L.EDIT_K else L.EDIT_LANES_NARROW
+    size = lambda t: L.lib().dicow_edit_alignment_ws_bytes(t.ctypes.data, len(t), int(lanes), int(along))     # noqa: E731
+    cap = L.ALIGN_MAX_WS_BYTES
+    whole = size(table)
+    if whole < 0 and b"DICOW_ALIGN_MAX_WS_BYTES" not in L.lib().dicow_last_error():
+        raise L.DicowError(f"edit_alignments: {L.lib().dicow_last_error().decode()}")
+    if 0 <= whole <= cap:
+        cuts = [0, n]
+    else:                                                                   # every byte of the workspace belongs to one pair: sizes add
+        cuts, used = [0], 0
+        for k in range(n):
+            need = size(table[k:k + 1])
+            if need < 0 or need > cap:
+                raise L.DicowError(f"edit_alignments: pair {k} ({int(table[k, 1])} x {int(table[k, 3])} words) needs more workspace for its "
+                                   f"records than DICOW_ALIGN_MAX_WS_BYTES = {cap} on its own")
+            if used + need > cap:
+                cuts.append(k)
+                used = 0
+            used += need
+        cuts.append(n)
+    eh, paths = [], []
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        part = np.ascontiguousarray(table[lo:hi])
+        out, path, spans = _alignment_call(ref_ids, hyp_ids, part, ref_iv, hyp_iv, lanes, along, size(part))
+        eh.append(out)
+        paths += [path[int(first):int(first + length)] for first, length in spans.tolist()]
+    return counts_from(torch.cat(eh), table), paths
+
+
+def alignment_chunks(path) -> list:
+    """The chunks of jiwer's ``process_words(...).alignments`` from one pair's ops: ``(type, ref_start, ref_end, hyp_start, hyp_end)`` with
+    ``type`` in ``equal substitute delete insert`` and half-open word ranges; neighbouring steps of one type are one chunk."""
+    out, i, j = [], 0, 0
+    for op in np.asarray(path, dtype=np.uint8).tolist():
+        di, dj = int(op != 3), int(op != 2)
+        if out and out[-1][0] == OPS[op]:
+            out[-1][2] += di
+            out[-1][4] += dj
+        else:
+            out.append([OPS[op], i, i + di, j, j + dj])
+        i, j = i + di, j + dj
+    return [tuple(c) for c in out]
+
+
+def alignment_rows(ref_words, hyp_words, path, ref_iv=None, hyp_iv=None) -> list:
+    """One pair's ops against its words: rows ``(op, ref_word, ref_begin_s, ref_end_s, hyp_word, hyp_begin_s, hyp_end_s)``, a missing side
+    ``None``; ``ref_iv`` / ``hyp_iv``: the words' (begin, end) ticks, or ``None`` for rows without times."""
+    path = np.asarray(path, dtype=np.uint8).tolist()
+    if sum(op != 3 for op in path) != len(ref_words) or sum(op != 2 for op in path) != len(hyp_words):
+        raise ValueError(f"alignment_rows: the ops do not span {len(ref_words)} reference and {len(hyp_words)} hypothesis words")
+    sec = lambda iv, k: (None, None) if iv is None else (iv[k][0] / TICKS_PER_SECOND, iv[k][1] / TICKS_PER_SECOND)     # noqa: E731
+    rows, i, j = [], 0, 0
+    for op in path:
+        r = (ref_words[i],) + sec(ref_iv, i) if op != 3 else (None, None, None)
+        h = (hyp_words[j],) + sec(hyp_iv, j) if op != 2 else (None, None, None)
+        rows.append((OPS[op],) + r + h)
+        i, j = i + (op != 3), j + (op != 2)
+    return rows
+
+
+def word_alignments(refs, hyps, text_norm: Optional[Callable] = None, unit: str = "word", device="cuda"):
+    """Lists of strings, one pair per utterance, as for ``word_error_counts`` -> ``(alignments, measures)``: per utterance the chunks of
+    jiwer's ``process_words(...).alignments`` (``alignment_chunks``), and jiwer's measures of the batch in that unit
+    (``measures_from_counts``), both from the same ``dicow_edit_alignment`` launch."""
+    rf, hf, table, _, _ = _utterance_pairs("word_alignments", refs, hyps, text_norm, unit, device)
+    counts, paths = edit_alignments(rf, hf, table)
+    tot = counts.sum(0)
+    return [alignment_chunks(p) for p in paths], measures_from_counts(tot[1], tot[2], tot[3], tot[4])
+
+
+def format_alignment(ref_words, hyp_words, path) -> str:
+    """Three lines of plain text, ``REF:`` / ``HYP:`` / marks (``S`` ``D`` ``I``, blank under a hit), every column as wide as the longer of
+    its two words, a missing word shown as ``*``.  The project's own layout, not jiwer's ``visualize_alignment``."""
+    ref_line, hyp_line, marks = [], [], []
+    for op, r, _, _, h, _, _ in alignment_rows(ref_words, hyp_words, path):
+        width = max(len(r or ""), len(h or ""), 1)
+        ref_line.append(("*" * width if r is None else r).ljust(width))
+        hyp_line.append(("*" * width if h is None else h).ljust(width))
+        marks.append({"equal": "", "substitute": "S", "delete": "D", "insert": "I"}[op].ljust(width))
+    return "\n".join((head + " ".join(cols)).rstrip() for head, cols in (("REF: ", ref_line), ("HYP: ", hyp_line), ("     ", marks)))
+
+
+def session_alignment(ref_segments, hyp_segments, timed: bool = True, collar: float = 5.0, device="cuda") -> dict:
+    """The data behind the reference's tcp alignment view (``calc_wer(save_visualizations=True)``, src/utils/wer.py:18-27, 154-155).  The
+    speaker assignment is ``tcp_wer``'s (``timed``) or ``cp_wer``'s: counts for all R x H pairs, Hungarian on the host; then ONE
+    ``edit_alignments`` call over the assigned pairs.  Returns that metric's result plus ``hits``, ``timed``, ``collar`` and ``speakers``:
+    per assigned pair ``{"ref_speaker", "hyp_speaker", "rows"}`` with rows ``(op, ref_word, ref_begin_s, ref_end_s, hyp_word, hyp_begin_s,
+    hyp_end_s)``, ``op`` in ``equal substitute delete insert``, the missing side ``None``, times from ``pseudo_word_intervals`` (the
+    hypothesis word's centre point widened by the collar).  A reference speaker without partner gives all ``delete`` rows and
+    ``hyp_speaker`` None; a hypothesis speaker without partner all ``insert`` rows and ``ref_speaker`` None.  The ops sum to the result's
+    ``substitutions`` / ``deletions`` / ``insertions``."""
+    result, c = _session_score(ref_segments, hyp_segments, timed, collar if timed else 0.0, device)
+    R, H = len(c["rk"]), len(c["hk"])
+    both = [i for i in range(R) if c["col"][i] < H]
+    paths = {}
+    if both:
+        table = np.array([(c["rs"][i], c["rl"][i], c["hs"][c["col"][i]], c["hl"][c["col"][i]]) for i in both], np.int64)
+        paths = dict(zip(both, edit_alignments(c["rf"], c["hf"], table, c["riv"], c["hiv"])[1]))
+    speakers, hits = [], 0
+    for i, j in enumerate(c["col"]):
+        rw, riv = c["ref"][c["rk"][i]] if i < R else ([], [])
+        hw, hiv = c["hyp"][c["hk"][j]] if j < H else ([], [])
+        path = paths[i] if i in paths else np.full(len(rw) + len(hw), 2 if rw else 3, np.uint8)
+        hits += int((np.asarray(path) == 0).sum())
+        speakers.append({"ref_speaker": c["rk"][i] if i < R else None, "hyp_speaker": c["hk"][j] if j < H else None,
+                         "rows": alignment_rows(rw, hw, path, riv, hiv)})
+    return {**result, "hits": hits, "timed": bool(timed), "collar": float(collar) if timed else None, "speakers": speakers}
+
+
+def error_breakdown(alignments, top: int = 20) -> dict:
+    """The most frequent errors of alignment rows: ``{"substitutions": [((ref_word, hyp_word), count)], "deletions": [(word, count)],
+    "insertions": [(word, count)]}``, at most ``top`` of each, by falling count, then lexicographically.  ``alignments``: a
+    ``session_alignment`` result, or any iterable of rows as ``alignment_rows`` gives them."""
+    if isinstance(alignments, dict):
+        alignments = (row for spk in alignments["speakers"] for row in spk["rows"])
+    tally = {"substitute": {}, "delete": {}, "insert": {}}
+    for row in alignments:
+        key = {"substitute": (row[1], row[4]), "delete": row[1], "insert": row[4]}.get(row[0])
+        if key is not None:
+            tally[row[0]][key] = tally[row[0]].get(key, 0) + 1
+    ranked = lambda d: sorted(d.items(), key=lambda kv: (-kv[1], kv[0]))[:top]     # noqa: E731
+    return {"substitutions": ranked(tally["substitute"]), "deletions": ranked(tally["delete"]), "insertions": ranked(tally["insert"])}
+
+
+def save_alignment_report(session_alignment: dict, path, top: int = 20) -> dict:
+    """One JSON file per session: the ``session_alignment`` result (rows as lists) plus ``breakdown`` (``error_breakdown``; a substituted
+    pair as ``[ref_word, hyp_word, count]``, a deleted or inserted word as ``[word, count]``).  Returns what was written."""
+    import json
+    b = error_breakdown(session_alignment, top)
+    report = {**session_alignment, "assignment": [list(p) for p in session_alignment["assignment"]],
+              "speakers": [{**spk, "rows": [list(r) for r in spk["rows"]]} for spk in session_alignment["speakers"]],
+              "breakdown": {"substitutions": [[r, h, n] for (r, h), n in b["substitutions"]],
+                            "deletions": [[w, n] for w, n in b["deletions"]], "insertions": [[w, n] for w, n in b["insertions"]]}}
+    with open(path, "w") as f:
+        json.dump(report, f, indent=1, ensure_ascii=False)
+    return report
