@@ -53,9 +53,10 @@ def prefix_score(x, rows, cs, decoded_len, last, r_prev, blank, eos):
             start = max(d, 1)
             acc = r[i, start - 1, 0, c]
             terms = [f32(phi[t] + xs[t + 1]) if (t + 1) >= d else LOGZERO for t in range(T - 1)]
-            m = max(terms)
-            lse = f32(m + np.log(np.sum(np.exp(np.array(terms, dtype=f32) - m, dtype=f32), dtype=f32), dtype=f32))
-            acc = _lae(acc, lse)
+            if terms:                                   # T = 1: torch.logsumexp over no frames is -inf and leaves acc as it is
+                m = max(terms)
+                lse = f32(m + np.log(np.sum(np.exp(np.array(terms, dtype=f32) - m, dtype=f32), dtype=f32), dtype=f32))
+                acc = _lae(acc, lse)
             for t in range(1, T):
                 r[i, t, 0, c] = f32(_lae(r[i, t - 1, 0, c], phi[t - 1]) + xs[t])
                 r[i, t, 1, c] = f32(_lae(r[i, t - 1, 0, c], r[i, t - 1, 1, c]) + xi[t, blank])

@@ -234,6 +234,8 @@ __global__ void __launch_bounds__(TSR_BLOCK) timestamp_rules_kernel(float* __res
     for (int v = tid; v < V; v += TSR_BLOCK) {
         if (banned(v)) continue;
         const float s = row[v];
+        if (s == -INFINITY) continue;                     // zero mass (a suppress list or the repetition rules ran first); with tm
+                                                          // still -inf the update below would form expf(-inf - -inf) = NaN
         if (v < ts0) mt = fmaxf(mt, s);
         else if (s > tm) { tsum = tsum * expf(tm - s) + 1.f; tm = s; }
         else tsum += expf(s - tm);
