@@ -175,7 +175,11 @@ int dicow_fddt_full_combine_bwd(const float* g, const float* stno, int64_t stno_
                                  /* so that the backward GEMM needs one multiply (MUL_AUX) and no transcendental    */
 #define DICOW_EPI_MUL_AUX  256   /* C = acc * aux[m,n]  (aux = saved gelu' from GELU_DAUX, bf16)                      */
 #define DICOW_EPI_COLSUM   512   /* colsum_out[n] += sum_m C[m,n] (bias gradient of the layer that produced the GEMM's */
-                                 /* input gradient); needs colsum_ws of dicow_gemm_nt_colsum_ws_bytes(M, N) bytes     */
+                                 /* input gradient); needs colsum_ws of dicow_gemm_nt_colsum_ws_bytes(M, N) bytes.     */
+                                 /* WHICH C is summed depends on the route: the persistent ring kernel's fused form (flags */
+                                 /* == MUL_AUX | COLSUM where dicow_gemm_nt_is_persistent) adds the fp32 results BEFORE    */
+                                 /* they are rounded to bf16 for the store; every other route adds the STORED bf16 values  */
+                                 /* (dicow_colsum_bf16 on C).  The two differ by the store rounding of each element.       */
 #define DICOW_EPI_FDDT    1024   /* with BIAS | RESIDUAL | OUT_F32: C = FDDT_next(bf16(acc + bias) + residual); persistent kernel only  */
 typedef struct {
     const void* A; const void* B; void* C;

@@ -299,9 +299,14 @@ def test_cast_transpose(ops, R, C, ld, ld_t):
     if ld: assert float(out[:, C:].float().abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("M,N,K", [(300, 256, 192), (6100, 2244, 128), (12200, 1284, 64),     # 128x128 / persistent 256x256 / 192x320
-                                   (16, 1284, 1280), (5, 260, 192),                            # skinny (M <= 16)
-                                   (12000, 508, 192)])                                         # 128x256 ring tiles (mid-size)
+# Routes (nt_plan of csrc/gemm.hip; not asserted here -- tests/test_gpu_gemm_epilogue_exact.py asserts the route of every case it runs):
+#   (300, 256, 192)    6 tiles of 128 x 128                      -> gemm_nt64_kernel<8> (64 x 64 tiles, 20 workgroups)
+#   (6100, 2244, 128)  216 tiles of 256 x 256                    -> gemm_ntr_kernel<F, 4, 4>; BIAS | GELU alone takes <3, 3, 5> (256 tiles of
+#                                                                   192 x 320 pad less and that epilogue accepts them at N > 2048)
+#   (12200, 1284, 64)  one k-step: the plan's `big` is false     -> gemm_nt_kernel<2, false>
+#   (16, 1284, 1280), (5, 260, 192)  M <= 16                     -> gemm_nt_skinny_kernel
+#   (12000, 508, 192)  376 tiles of 128 x 128, 94 of 256 x 256   -> gemm_nt128t_kernel
+@pytest.mark.parametrize("M,N,K", [(300, 256, 192), (6100, 2244, 128), (12200, 1284, 64), (16, 1284, 1280), (5, 260, 192), (12000, 508, 192)])
 def test_gemm_nt_epilogues(ops, M, N, K):
     from ts_asr_whisper_amd import _lib as L
     g = torch.Generator().manual_seed(5)
