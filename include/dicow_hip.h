@@ -810,6 +810,49 @@ int dicow_repetition_rules(float* scores, int64_t ld, int rows, int V, const int
 int dicow_ctc_greedy_decode(const void* logits, int in_bf16, int64_t batch_stride, int64_t ld, int B, int Tn, int V1, int64_t blank,
                             int64_t pad_id, int* ws, int64_t* out, int64_t out_stride, void* stream);
 
+/* CTC forced alignment (ABI 7, additive): the best path through the CTC trellis of a KNOWN target sequence, read back -- what
+ * torchaudio.functional.forced_align computes -- for n independent problems in one call (all decoded segments of a session).
+ * logits fp32 / bf16 (in_bf16) [B, T, ld >= V1], frame-major with dense frames, read in place; columns [V1, ld) and frames outside a
+ * problem's slice are never read.  lse fp32 [B * T] (dicow_ctc_frame_lse) or NULL: the logits are log-probabilities already.  alias int32
+ * [V1] or NULL (identity), as for dicow_ctc_prefix_score; an alias outside [0, V1) counts as -inf.
+ * table: a HOST int64 [n][5] table of (row, f0, F, target_offset, L); targets: a HOST int32 array of n_targets ids.  Problem i aligns
+ * y = targets[target_offset .. + L) against frames [f0, f0 + F) of logits row `row` with x[f][c] = logit[row, f0 + f, alias[c]] -
+ * lse[row * T + f0 + f] (one fp32 subtraction).  States s = 0 .. 2 L, even = blank, odd = y[(s - 1) / 2]:
+ *   v[0][0] = x[0][blank], v[0][1] = x[0][y[0]], every other v[0][s] = -inf,
+ *   v[f][s] = x[f][label(s)] + max over the admissible predecessors of v[f - 1][.]        (plain fp32 addition),
+ * the predecessors being s, s - 1, and s - 2 when s is odd and y[(s - 1) / 2] != y[(s - 3) / 2].
+ * THE TIE RULE is the project's own (it is not pinned to any other implementation): among equal maxima staying in s beats s - 1 and s - 1
+ * beats s - 2; at the last frame state 2 L wins over 2 L - 1 only if strictly greater; L = 0 gives the all-blank path; F = 0 with L = 0
+ * the empty path of score 0.  -inf logits are legal.  NaN among the used columns is outside the contract (nothing is read or written out
+ * of bounds).  Outputs, all device buffers, one writer per element, no atomics:
+ *   path        int32 [n, Fmax]     the label id of every frame (`blank` on blank frames), -1 from F to Fmax;
+ *   spans       int32 [n, Lmax, 2]  (first frame, one past the last frame) of every target, relative to f0; -1 behind L;
+ *   token_score fp32  [n, Lmax]     the sum of x over the target's own frames, added in ascending frame order; 0 behind L;
+ *   score       fp32  [n]           v at the chosen end state;
+ *   status      int32 [n]           0 aligned; 1 infeasible: F < L + (number of adjacent equal targets), F = 0 with L > 0, or every end state
+ *                                   at -inf.  An infeasible problem has -1 in its whole path and all its spans, 0 token scores, score -inf.
+ * A problem's bits do not depend on plan or on the other problems of the call.
+ * Launches: a gather of the compact emission matrix E (per problem F rows of W = roundup8(L) + 4 floats: the targets' x, -inf up to a
+ * multiple of 8, the blank's x, three zeros), then one wave per problem: the frame recursion with 16 (wide plan) or 2 (narrow plan, L <=
+ * 63) states per lane in registers, 2-bit back-pointers stored per frame, and the walk back through blocks of 64 frames of them staged in
+ * LDS.  plan: 0 = narrow for every problem with L <= 63, wide otherwise; 1 / 2 force narrow / wide (tests, measurements).  One copy (the
+ * tables, into ws, on the stream) and two launches; no host read: the call can be captured into a graph.
+ * ws: dicow_ctc_align_ws_bytes(table, n) bytes, 16-byte aligned, at most DICOW_CTC_ALIGN_MAX_WS_BYTES: DICOW_CTC_ALIGN_PROB_BYTES a problem
+ * plus 4 bytes a target, rounded up to 16; then per problem 4 F W bytes of E and F * bp_row rounded up to 16 of back-pointers, bp_row =
+ * max(4 * ceil((2 L + 1) / 16), roundup4(L + 1) if L <= 63).
+ * Checked on the host before anything is launched (-1, dicow_last_error() names the limit): row in [0, B); f0 >= 0 and f0 + F <= T; F in
+ * [0, 2^31); L <= DICOW_CTC_ALIGN_MAX_L (2 L + 1 <= 1024 states, the ceiling of dicow_ctc_args.Smax); the targets' range in the array, every
+ * id in [0, V1) and not `blank`; Fmax / Lmax not below the table's largest F / L; plan; the workspace limit; pointers and their alignment;
+ * ws_bytes.  dicow_ctc_align_ws_bytes checks F, L and the limit alone and returns -1 where the call would refuse them.  n == 0 launches
+ * nothing. */
+#define DICOW_CTC_ALIGN_MAX_L 511
+#define DICOW_CTC_ALIGN_MAX_WS_BYTES 1073741824LL
+#define DICOW_CTC_ALIGN_PROB_BYTES 56
+int64_t dicow_ctc_align_ws_bytes(const int64_t* table, int n);
+int dicow_ctc_forced_align(const void* logits, int in_bf16, int B, int T, int V1, int64_t ld, const float* lse, const int32_t* alias, int blank,
+                           const int64_t* table, int n, const int32_t* targets, int64_t n_targets, int32_t* path, int Fmax, int32_t* spans,
+                           int Lmax, float* token_score, float* score, int32_t* status, int plan, void* ws, int64_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ optimizer
  * Fused AdamW + global-norm clipping on flat fp32 regions (src/models/containers.py:100-114 two param groups;
  * HF Trainer max_grad_norm 1.0).  dicow_sumsq_f32 accumulates sum(x^2) into out[0], DETERMINISTICALLY for a given input

@@ -13,6 +13,8 @@ from .modeling import (FDDT, DiCoWEncoder, DiCoW, DiCoWForConditionalGeneration,
                        shift_tokens_right, build_ts_tables, LoRALinear, add_decoder_lora, merge_lora, save_adapter, load_adapter,
                        freeze_for_ctc_pretraining)
 from .ctc_decoding import ctc_greedy_decode, chunked_ctc_logits  # noqa: F401
+from .ctc_align import (CtcAlignment, ctc_forced_align, token_timestamps, word_timestamps, align_segments,  # noqa: F401
+                        words_as_segments)
 from .wave_augment import NoiseBank, plan_background_noise, mix_background_noise, WaveFrontEnd  # noqa: F401
 from .diar_front_end import (SpeakerSegments, stno_masks, select_enrollment_windows, draw_enrollment_window,  # noqa: F401
                              MeetingFrontEnd)
@@ -41,4 +43,5 @@ __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalG
            "session_metrics", "aggregate_session_metrics", "edit_alignments", "alignment_chunks", "alignment_rows", "word_alignments",
            "format_alignment", "session_alignment", "error_breakdown", "save_alignment_report", "unscored_intervals", "diar_score_counts", "split_counts", "mapping_from_counts",
            "error_from_counts", "jaccard_from_counts", "aggregate_diarization_scores", "diarization_error", "jaccard_error", "optimal_mapping",
-           "score_diarizations"]
+           "score_diarizations", "CtcAlignment", "ctc_forced_align", "token_timestamps", "word_timestamps", "align_segments",
+           "words_as_segments"]

@@ -81,6 +81,9 @@ EDIT_MAX_LEN, EDIT_K, EDIT_LANES, EDIT_LANES_NARROW = 65535, 8, 512, 64   # DICO
 
 ALIGN_MAX_WS_BYTES, ALIGN_TABLE_BYTES = 1 << 30, 56   # DICOW_ALIGN_*: dicow_edit_alignment's workspace limit and its tables' bytes per pair
 
+# DICOW_CTC_ALIGN_*: dicow_ctc_forced_align's longest target sequence, workspace limit and table bytes per problem
+CTC_ALIGN_MAX_L, CTC_ALIGN_MAX_WS_BYTES, CTC_ALIGN_PROB_BYTES = 511, 1 << 30, 56
+
 # DICOW_ORC_*: dicow_orc_distance's limits, chunk and descriptor sizes
 ORC_MAX_STREAMS, ORC_K, ORC_MAX_WORDS, ORC_MAX_STATES, ORC_MAX_WS_BYTES, ORC_DESC_BYTES, ORC_UTT_BYTES = 8, 8, 65527, 1 << 22, 1 << 30, 288, 16
 
@@ -203,6 +206,8 @@ _SIGS = {
     "dicow_whisper_timestamp_rules": [c_vp, c_i64, c_i, c_i, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
     "dicow_repetition_rules": [c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_i, c_f, c_i, c_vp],
     "dicow_ctc_greedy_decode": [c_vp, c_i, c_i64, c_i64, c_i, c_i, c_i, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp],
+    "dicow_ctc_forced_align": [c_vp, c_i, c_i, c_i, c_i, c_i64, c_vp, c_vp, c_i, c_vp, c_i, c_vp, c_i64, c_vp, c_i, c_vp, c_i, c_vp, c_vp, c_vp,
+                               c_i, c_vp, c_i64, c_vp],
     "dicow_noise_mix": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i64, c_vp],
     "dicow_diar_frame_counts": [c_vp, c_vp, c_i, c_i, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp],
     "dicow_stno_from_counts": [c_vp, c_i, c_i64, c_vp, c_i, c_vp, c_i64, c_vp, c_i64, c_vp],
@@ -298,6 +303,7 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
     "dicow_resample_ws_bytes": [c_i, c_i],
     "dicow_edit_distance_ws_bytes": [c_vp, c_i],
     "dicow_edit_alignment_ws_bytes": [c_vp, c_i, c_i, c_i],
+    "dicow_ctc_align_ws_bytes": [c_vp, c_i],
     "dicow_orc_distance_ws_bytes": [c_vp, c_i, c_vp, c_vp, c_i],
     "dicow_diar_score_ws_bytes": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i],
 }
