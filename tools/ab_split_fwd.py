@@ -35,7 +35,7 @@ engine.SPLIT_FWD = False; r1 = enc(b["input_features"], stno_mask=b["stno_mask"]
 engine.SPLIT_FWD = True; r2 = enc(b["input_features"], stno_mask=b["stno_mask"]).last_hidden_state.detach().clone()
 print("training-form output, two streams vs one: bit-equal =", bool(torch.equal(r1, r2)), "; vs inference form:", bool(torch.equal(r1, ref)))
 for rnd in range(int(sys.argv[1]) if len(sys.argv) > 1 else 2):
-    for name, on, parts in (("one stream", False, 2), ("two streams", True, 2), ("four streams", True, 4)):
-        engine.SPLIT_FWD, engine.SPLIT_FWD_PARTS = on, parts
+    for name, on in (("one stream", False), ("two streams", True)):
+        engine.SPLIT_FWD = on
         tt, ti = timed(True), timed(False)
         print(f"{name:14s} training form {tt:6.2f} ms = {flops / tt / 1e9 / 2500:.4f} of 2.5 PF   inference form {ti:6.2f} ms = {flops / ti / 1e9 / 2500:.4f}", flush=True)

@@ -33,26 +33,6 @@ def _ceil(a, b):
     return (a + b - 1) // b * b
 
 
-# Weight gradients beside the gradient chain (round 6).  The pooled weight-gradient launch of a layer (ops.TnGroup.run) is off the critical
-# path: nothing in the backward pass reads a dW.  With WGRAD_SIDE_STREAM it is enqueued on a second HIP stream behind an event that says
-# "this layer's operands are written", and the next layer's dgrad chain starts at once: the HBM-bound row kernels, the attention kernel's
-# half-empty last round and the GEMM tails of the chain run beside a matrix-bound kernel instead of after it.  Same kernels, same operands,
-# one writer per dW: bit-identical to the one-stream order.  The side stream is a PRIORITY stream (a queue of its own: a normal-priority pool
-# stream may share the compute stream's hardware queue, profiles/r06_streams.txt); the backward pass joins it before it returns.
-WGRAD_SIDE_STREAM = os.environ.get("DICOW_WGRAD_STREAM", "0") == "1"
-WGRAD_STREAM_PRIORITY = int(os.environ.get("DICOW_WGRAD_STREAM_PRIORITY", "-1"))
-_WGRAD_STREAMS = {}
-
-
-def wgrad_stream(dev):
-    cur = torch.cuda.current_stream(dev)
-    key = (dev.index, cur.cuda_stream)
-    st = _WGRAD_STREAMS.get(key)
-    if st is None:
-        st = _WGRAD_STREAMS[key] = torch.cuda.Stream(device=dev, priority=WGRAD_STREAM_PRIORITY)
-    return st
-
-
 # The encoder FORWARD of a large even batch as two half batches on two HIP streams, into the halves of the SAME full-batch activation
 # buffers (rows are batch-major: a half batch is a contiguous row range of every buffer).  Every forward kernel is row-parallel, so
 # the results are bit-identical to the one-stream forward; the HBM-bound row kernels, the attention tails and the partial last rounds
@@ -64,15 +44,16 @@ SPLIT_FWD = os.environ.get("DICOW_SPLIT_FWD", "1") != "0"
 SPLIT_FWD_MIN_ROWS = int(os.environ.get("DICOW_SPLIT_FWD_MIN_ROWS", "16000"))      # whisper-base B = 8 (12000 rows, one hipGraph) stays on one stream
 SPLIT_DEC = os.environ.get("DICOW_SPLIT_DEC", "1") != "0"                     # the FROZEN decoder's layers too (forward and backward: DecoderEngine)
 SPLIT_BWD = os.environ.get("DICOW_SPLIT_BWD", "1") != "0"                     # the encoder BACKWARD's row-parallel chain as two halves too (EncoderEngine._backward_split)
-SPLIT_BWD_WGRAD = os.environ.get("DICOW_SPLIT_BWD_WGRAD", "alt")               # which stream launches a layer's pooled weight gradients: "alt" = odd layers on the side stream (the streams carry equal work: 124.5-124.6 ms per step) | "main" (124.7-124.9; one stream 126.3) | "third" = every pooled launch on a third queue, settled one layer later still (measured +1.5 ms: 129.5 against 127.9-128.1, profiles/r06_split_bwd.txt)
+SPLIT_BWD_WGRAD = os.environ.get("DICOW_SPLIT_BWD_WGRAD", "alt")               # which stream launches a layer's pooled weight gradients: "alt" = odd layers on the side stream (the streams carry equal work: 124.5-124.6 ms per step) | "main" (124.7-124.9; one stream 126.3)
 SPLIT_BWD_MEM_FRACTION = float(os.environ.get("DICOW_SPLIT_BWD_MEM_FRACTION", "0.6"))   # the split backward only if its buffers fit into this share of the free memory
-SPLIT_IN_CAPTURE = os.environ.get("DICOW_SPLIT_IN_CAPTURE", "0") == "1"      # experiment: fork the two half-batch streams inside a hipGraph capture too (parallel branches of the graph)
-SPLIT_FWD_PARTS = int(os.environ.get("DICOW_SPLIT_FWD_PARTS", "2"))          # (4 measured against 2: profiles/r06_split_fwd.txt)
 _FWD_STREAMS = {}
+if SPLIT_BWD_WGRAD not in ("alt", "main"):
+    raise ValueError(f"DICOW_SPLIT_BWD_WGRAD must be 'alt' or 'main', not {SPLIT_BWD_WGRAD!r}")
 
 
 def _split_allowed():
-    return SPLIT_IN_CAPTURE or not torch.cuda.is_current_stream_capturing()
+    """The half-batch streams are never forked under stream capture: a captured step stays one chain on the capturing stream."""
+    return not torch.cuda.is_current_stream_capturing()
 
 
 def fwd_side_stream(dev, k=0):
@@ -85,16 +66,19 @@ def fwd_side_stream(dev, k=0):
 
 
 def _fwd_parts(B, T, dev):
-    """[(stream, row slice, batch slice)] of the forward's parts: part 0 on the caller's stream, the others on side streams (forked here)."""
-    n = SPLIT_FWD_PARTS if (SPLIT_FWD_PARTS > 2 and B % SPLIT_FWD_PARTS == 0) else 2
-    main_st, Bp = torch.cuda.current_stream(dev), B // n
-    parts = []
-    for k in range(n):
-        st = main_st if k == 0 else fwd_side_stream(dev, k - 1)
-        if k:
-            st.wait_stream(main_st)
-        parts.append((st, slice(k * Bp * T, (k + 1) * Bp * T), slice(k * Bp, (k + 1) * Bp)))
-    return main_st, parts, Bp
+    """[(stream, row slice, batch slice)] of the two half batches: half 0 on the caller's stream, half 1 on the side stream (forked here)."""
+    main_st, side_st, Bh = torch.cuda.current_stream(dev), fwd_side_stream(dev), B // 2
+    side_st.wait_stream(main_st)
+    return main_st, [(main_st, slice(0, Bh * T), slice(0, Bh)), (side_st, slice(Bh * T, B * T), slice(Bh, B))], Bh
+
+
+def _one_part(B):
+    """The one-stream case in the shape of _fwd_parts' list: every row, on the current stream."""
+    return ((None, slice(None), slice(0, B)),)
+
+
+def _on(st):
+    return torch.cuda.stream(st) if st is not None else contextlib.nullcontext()
 
 
 class GradSink:
@@ -269,8 +253,7 @@ def full_fddt_bwd(fddt, w, hb, g, stno, bstride, G, rows, T, D):
 # head_dim^-0.5 * log2 e) -- ONE rounding, like the reference's bf16(Wx + b) * head_dim^-0.5, but not the same one), so the forward
 # kernel's probabilities are p = 2^s with no arithmetic in front of the exponential and the backward kernels lose their per-score
 # multiply.  Same softmax, same lse (natural log), same gradients; dq_scale keeps its meaning (include/dicow_hip.h).
-# (DICOW_QK_LOG2=0 in the environment selects the plain form for A/B runs -- tools used to edit this file in place.)
-QK_LOG2 = os.environ.get("DICOW_QK_LOG2", "1") != "0"
+QK_LOG2 = True
 FUSE_NEXT_FDDT = True         # inference forward: the next layer's diagonal FDDT in the fc2 epilogue (see EncoderEngine.forward)
 # LayerNorm folded into the GEMMs on either side of it (round 4; include/dicow_hip.h, DICOW_EPI_LNSTAT / LNFOLD): out-proj / fc2
 # also store bf16(h) and per-row partial statistics, qkv / fc1 read bf16(h) against gamma-scaled weights and normalise in their
@@ -422,59 +405,124 @@ def heads(t, B, Lx, H):
 
 
 # ------------------------------------------------------------------------------------------------ encoder
+# The plain pre-LN encoder layer (HF WhisperEncoderLayer, a diagonal FDDT in front of its first LayerNorm when it has one) is written ONCE per
+# direction, as a chain over a row range r (= the Bh batch entries bsl) of full-size buffers, on the current stream.  Its drivers decide which
+# rows, which stream, where the vector gradients land and when the weight gradients run: plain_layer_fwd / plain_layer_bwd (the CTC branch),
+# EncoderEngine._forward_impl / backward (all rows, or the two half batches of SPLIT_FWD) and EncoderEngine._backward_split.  r = slice(None),
+# bsl = slice(0, B) give the kernels the buffers themselves: same pointers, strides and STNO offset as an unsliced call.
+def _fddt_kw(fddt, bsl, T):
+    """The row kernels' FDDT keywords for the batch entries bsl.  fddt: None (a layer without: the kernels' defaults) or (mode, w[4], b[4],
+    stno, bstride) with fddt_ptrs' first three; bstride // (4 T) STNO entries belong to one batch entry (2 once the enrollment rows are gone)."""
+    if fddt is None:
+        return {}
+    mode, fw, fb, stno, bstride = fddt
+    return dict(mode=mode, stno=stno[bsl.start * (bstride // (4 * T)):], stno_bstride=bstride, T=T, w=fw, b=fb)
+
+
+def layer_fwd_buffers(Ls, B, T, H, F_, own_hp):
+    """The activations a plain layer keeps for its backward pass, allocated into Ls next to its input Ls.h_in; returns the buffer of the
+    layer's output.  own_hp: an FDDT changes the residual stream, h' gets a buffer of its own (else it IS the input)."""
+    h = Ls.h_in
+    (rows, D), dev = h.shape, h.device
+    Ls.xln, Ls.mean, Ls.rstd = _e((rows, D), BF16, dev), _e((rows,), F32, dev), _e((rows,), F32, dev)
+    Ls.hp = _e((rows, D), F32, dev) if own_hp else h
+    Ls.qkv, Ls.o, Ls.lse = _e((rows, 3 * D), BF16, dev), _e((rows, D), BF16, dev), _e((B, H, T), F32, dev)
+    Ls.h2, Ls.xln2 = _e((rows, D), F32, dev), _e((rows, D), BF16, dev)
+    Ls.mean2, Ls.rstd2 = _e((rows,), F32, dev), _e((rows,), F32, dev)
+    Ls.u, Ls.a = _e((rows, F_), BF16, dev), _e((rows, F_), BF16, dev)     # u = gelu'(pre-activation), consumed by the backward pass
+    return _e((rows, D), F32, dev)
+
+
+def layer_rows_fwd(lyr, w, Ls, hn, r, bsl, Bh, T, H, fddt=None):
+    """Rows r of a plain layer's training forward: LayerNorm1 (+ FDDT), qkv, attention (q pre-scaled in the projection epilogue, in base-2
+    units: Q_SCALE above), out-proj + residual, LayerNorm2, fc1 + GELU (gelu' kept), fc2 + residual -> hn[r]."""
+    rh, D = Bh * T, Ls.xln.shape[1]
+    ln, ln2 = lyr.self_attn_layer_norm, lyr.final_layer_norm
+    ops.fddt_ln_fwd(Ls.h_in[r], rh, D, h_out=Ls.hp[r] if Ls.hp is not Ls.h_in else None, ln_w=ln.weight.detach(), ln_b=ln.bias.detach(),
+                    y_bf16=Ls.xln[r], mean=Ls.mean[r], rstd=Ls.rstd[r], **_fddt_kw(fddt, bsl, T))
+    qkv, o = Ls.qkv[r], Ls.o[r]
+    linear_fwd(Ls.xln[r], w.att.qkv, rh, flags=L.EPI_SCALE_N, scale=Q_SCALE, scale_ncols=D, out=qkv)
+    ops.attn_fwd(heads(qkv[:, :D], Bh, T, H), heads(qkv[:, D:2 * D], Bh, T, H), heads(qkv[:, 2 * D:], Bh, T, H), heads(o, Bh, T, H),
+                 Ls.lse[bsl], q_log2=QK_LOG2)
+    linear_fwd(o, w.att.o, rh, out_dtype=F32, residual=Ls.hp[r], out=Ls.h2[r])
+    ops.fddt_ln_fwd(Ls.h2[r], rh, D, mode=ops.MODE_NONE, ln_w=ln2.weight.detach(), ln_b=ln2.bias.detach(), y_bf16=Ls.xln2[r],
+                    mean=Ls.mean2[r], rstd=Ls.rstd2[r])
+    linear_fwd(Ls.xln2[r], w.fc1, rh, gelu_aux=Ls.u[r], out=Ls.a[r])
+    linear_fwd(Ls.a[r], w.fc2, rh, out_dtype=F32, residual=Ls.h2[r], out=hn[r])
+
+
+def layer_bwd_buffers(rows, D, F_, dev, tail=True, g0b=True):
+    """The gradient buffers of one layer's backward chain, full size.  tail: the chain ends with the LayerNorm1 (+ FDDT) backward into g0
+    (fp32) and, unless the layer is the lowest one, g0b (its bf16 copy: the dgrad / weight-gradient operand of the layer below)."""
+    bf = NS()
+    bf.d_u, bf.d_xln2 = _e((rows, F_), BF16, dev), _e((rows, D), BF16, dev)
+    bf.g2, bf.g2b, bf.d_o = _e((rows, D), F32, dev), _e((rows, D), BF16, dev), _e((rows, D), BF16, dev)
+    bf.d_qkv, bf.d_xln = _e((rows, 3 * D), BF16, dev), _e((rows, D), BF16, dev)
+    bf.g0 = _e((rows, D), F32, dev) if tail else None
+    bf.g0b = _e((rows, D), BF16, dev) if (tail and g0b) else None
+    return bf
+
+
+def layer_rows_bwd(lyr, w, Ls, bf, r, bsl, Bh, T, H, g, gb, gg, tail=True, fddt=None, prev_b2=None):
+    """Rows r of a layer's backward chain.  g / gb: fp32 / bf16 gradient wrt the layer's output; gg(param) -> where that parameter's
+    row reductions land (None: skipped).  fc2 dgrad with the fused gelu', fc1 dgrad, LayerNorm2 backward, out-proj dgrad, attention
+    backward, qkv dgrad; the bias gradients are the fused column sums of those kernels.  tail (a plain layer: no speaker-communication
+    block, no dense FDDT between its input and LayerNorm1): also the LayerNorm1 (+ FDDT) backward into bf.g0 / bf.g0b, whose column sum is
+    the bias gradient of the fc2 below (prev_b2); otherwise the caller goes on from bf.d_xln and bf.g2.  Returns the attention's scratch."""
+    rh, D = Bh * T, gb.shape[1]
+    att, ln, ln2 = lyr.self_attn, lyr.self_attn_layer_norm, lyr.final_layer_norm
+    linear_dgrad(gb[r], w.fc2, rh, aux=Ls.u[r], colsum_out=gg(lyr.fc1.bias), out=bf.d_u[r])
+    linear_dgrad(bf.d_u[r], w.fc1, rh, out=bf.d_xln2[r])
+    ops.fddt_ln_bwd(Ls.h2[r], rh, D, mode=ops.MODE_NONE, ln_w=ln2.weight.detach(), mean=Ls.mean2[r], rstd=Ls.rstd2[r], d_y=bf.d_xln2[r],
+                    g_res=g[r], g_out=bf.g2[r], g_out_bf16=bf.g2b[r], dln_w=gg(ln2.weight), dln_b=gg(ln2.bias),
+                    colsum_out=gg(att.out_proj.bias))
+    linear_dgrad(bf.g2b[r], w.att.o, rh, out=bf.d_o[r])
+    delta = _e((2, Bh, H, T), F32, gb.device)
+    qkv, d_qkv = Ls.qkv[r], bf.d_qkv[r]
+    ops.attn_bwd(heads(qkv[:, :D], Bh, T, H), heads(qkv[:, D:2 * D], Bh, T, H), heads(qkv[:, 2 * D:], Bh, T, H), heads(Ls.o[r], Bh, T, H),
+                 heads(bf.d_o[r], Bh, T, H), Ls.lse[bsl], delta, heads(d_qkv[:, :D], Bh, T, H), heads(d_qkv[:, D:2 * D], Bh, T, H),
+                 heads(d_qkv[:, 2 * D:], Bh, T, H), dq_scale=0.125, q_log2=QK_LOG2, dq_colsum=gg(att.q_proj.bias),
+                 dv_colsum=gg(att.v_proj.bias))
+    linear_dgrad(d_qkv, w.att.qkv, rh, out=bf.d_xln[r])
+    if tail:
+        fk = _fddt_kw(fddt, bsl, T)
+        if fddt is not None:
+            fk.update(dw=tuple(gg(x) for x in fddt[1]), db=tuple(gg(x) for x in fddt[2]))
+        ops.fddt_ln_bwd(Ls.h_in[r], rh, D, ln_w=ln.weight.detach(), mean=Ls.mean[r], rstd=Ls.rstd[r], d_y=bf.d_xln[r], g_res=bf.g2[r],
+                        g_out=bf.g0[r], g_out_bf16=bf.g0b[r] if bf.g0b is not None else None, dln_w=gg(ln.weight), dln_b=gg(ln.bias),
+                        colsum_out=gg(prev_b2), **fk)
+    return delta
+
+
+def layer_wgrads(lyr, Ls, bf, gb, G, rows, group=None):
+    """The four weight-gradient GEMMs of a layer over ALL rows, in the one order every driver keeps (_first_writer consumes its flags in
+    call order): fc2, fc1, out-proj, fused q/k/v -- recorded into `group` (the operands must stay untouched until group.run()) or run."""
+    att = lyr.self_attn
+    linear_wgrad(gb, Ls.a, G.get(lyr.fc2.weight), rows, group=group, param=lyr.fc2.weight)
+    linear_wgrad(bf.d_u, Ls.xln2, G.get(lyr.fc1.weight), rows, group=group, param=lyr.fc1.weight)
+    linear_wgrad(bf.g2b, Ls.o, G.get(att.out_proj.weight), rows, group=group, param=att.out_proj.weight)
+    qkv_wgrad(bf.d_qkv, Ls.xln, G.get(att.q_proj.weight), G.get(att.k_proj.weight), G.get(att.v_proj.weight), rows, gb.shape[1], group=group,
+              params=(att.q_proj.weight, att.k_proj.weight, att.v_proj.weight))
+
+
 def plain_layer_fwd(lyr, w, h, B, T, H, F_):
     """One pre-LN Whisper encoder layer without FDDT / SCB on fp32 rows ``h`` [B*T, D] (HF WhisperEncoderLayer; the CTC
     branch's ``additional_layer``, reference encoder.py:16-17,88-94).  Returns (fp32 rows, saved activations)."""
-    rows, D = h.shape
-    dev = h.device
     s = NS(h_in=h)
-    s.xln, s.mean, s.rstd = _e((rows, D), BF16, dev), _e((rows,), F32, dev), _e((rows,), F32, dev)
-    ln = lyr.self_attn_layer_norm
-    ops.fddt_ln_fwd(h, rows, D, mode=ops.MODE_NONE, ln_w=ln.weight.detach(), ln_b=ln.bias.detach(), y_bf16=s.xln, mean=s.mean,
-                    rstd=s.rstd)
-    s.qkv = linear_fwd(s.xln, w.att.qkv, rows, flags=L.EPI_SCALE_N, scale=Q_SCALE, scale_ncols=D)
-    s.o, s.lse = _e((rows, D), BF16, dev), _e((B, H, T), F32, dev)
-    ops.attn_fwd(heads(s.qkv[:, :D], B, T, H), heads(s.qkv[:, D:2 * D], B, T, H), heads(s.qkv[:, 2 * D:], B, T, H),
-                 heads(s.o, B, T, H), s.lse, q_log2=QK_LOG2)
-    s.h2 = linear_fwd(s.o, w.att.o, rows, out_dtype=F32, residual=h)
-    s.xln2, s.mean2, s.rstd2 = _e((rows, D), BF16, dev), _e((rows,), F32, dev), _e((rows,), F32, dev)
-    ln2 = lyr.final_layer_norm
-    ops.fddt_ln_fwd(s.h2, rows, D, mode=ops.MODE_NONE, ln_w=ln2.weight.detach(), ln_b=ln2.bias.detach(), y_bf16=s.xln2,
-                    mean=s.mean2, rstd=s.rstd2)
-    s.u = _e((rows, F_), BF16, dev)
-    s.a = linear_fwd(s.xln2, w.fc1, rows, gelu_aux=s.u)
-    return linear_fwd(s.a, w.fc2, rows, out_dtype=F32, residual=s.h2), s
+    hn = layer_fwd_buffers(s, B, T, H, F_, own_hp=False)
+    layer_rows_fwd(lyr, w, s, hn, slice(None), slice(0, B), B, T, H)
+    return hn, s
 
 
 def plain_layer_bwd(lyr, w, s, gb, G, B, T, H):
     """Backward of plain_layer_fwd.  gb: bf16 rows, gradient wrt the layer output.  Returns the fp32 gradient wrt its input."""
     rows, D = gb.shape
-    dev = gb.device
     g = gb.float()
     bias_grad(gb, G.get(lyr.fc2.bias))
-    linear_wgrad(gb, s.a, G.get(lyr.fc2.weight), rows)
-    d_u = linear_dgrad(gb, w.fc2, rows, aux=s.u, colsum_out=G.get(lyr.fc1.bias))
-    linear_wgrad(d_u, s.xln2, G.get(lyr.fc1.weight), rows)
-    d_xln2 = linear_dgrad(d_u, w.fc1, rows)
-    g2, g2b = _e((rows, D), F32, dev), _e((rows, D), BF16, dev)
-    ln2, att = lyr.final_layer_norm, lyr.self_attn
-    ops.fddt_ln_bwd(s.h2, rows, D, mode=ops.MODE_NONE, ln_w=ln2.weight.detach(), mean=s.mean2, rstd=s.rstd2, d_y=d_xln2, g_res=g,
-                    g_out=g2, g_out_bf16=g2b, dln_w=G.get(ln2.weight), dln_b=G.get(ln2.bias), colsum_out=G.get(att.out_proj.bias))
-    linear_wgrad(g2b, s.o, G.get(att.out_proj.weight), rows)
-    d_o = linear_dgrad(g2b, w.att.o, rows)
-    d_qkv, delta = _e((rows, 3 * D), BF16, dev), _e((2, B, H, T), F32, dev)
-    qkv = s.qkv
-    ops.attn_bwd(heads(qkv[:, :D], B, T, H), heads(qkv[:, D:2 * D], B, T, H), heads(qkv[:, 2 * D:], B, T, H),
-                 heads(s.o, B, T, H), heads(d_o, B, T, H), s.lse, delta, heads(d_qkv[:, :D], B, T, H),
-                 heads(d_qkv[:, D:2 * D], B, T, H), heads(d_qkv[:, 2 * D:], B, T, H), dq_scale=0.125, q_log2=QK_LOG2,
-                 dq_colsum=G.get(att.q_proj.bias), dv_colsum=G.get(att.v_proj.bias))
-    qkv_wgrad(d_qkv, s.xln, G.get(att.q_proj.weight), G.get(att.k_proj.weight), G.get(att.v_proj.weight), rows, D)
-    d_xln = linear_dgrad(d_qkv, w.att.qkv, rows)
-    g0 = _e((rows, D), F32, dev)
-    ln = lyr.self_attn_layer_norm
-    ops.fddt_ln_bwd(s.h_in, rows, D, mode=ops.MODE_NONE, ln_w=ln.weight.detach(), mean=s.mean, rstd=s.rstd, d_y=d_xln, g_res=g2,
-                    g_out=g0, dln_w=G.get(ln.weight), dln_b=G.get(ln.bias))
-    return g0
+    bf = layer_bwd_buffers(rows, D, w.fc1.N, gb.device, g0b=False)
+    layer_rows_bwd(lyr, w, s, bf, slice(None), slice(0, B), B, T, H, g, gb, G.get)
+    layer_wgrads(lyr, s, bf, gb, G, rows)
+    return bf.g0
 
 
 def conv_stem_fwd(enc, W, input_features, need_grad=True):
@@ -682,47 +730,27 @@ class EncoderEngine:
             Ls = NS(h_in=h, B=Bc, bstride=bstride)
             rows = Bc * T
             if split_ok and halves is None and i == split_from and Bc % 2 == 0 and rows >= SPLIT_FWD_MIN_ROWS:
-                S.split_from, S.split_sstep = i, bstride // (4 * T)   # (the split backward covers the same layers: their saved buffers are full-batch, no SCB)
-                main_st, halves, Bh = _fwd_parts(Bc, T, dev)      # fork: h (stem + initial FDDT, or the last speaker-communication layer) is complete
-                rh, sstep = Bh * T, bstride // (4 * T)             # (sstep: STNO rows per encoder row -- 2 once the enrollment rows are gone)
-            if halves is not None:
-                fd = enc.fddts[i] if (cfg.use_fddt and i < len(enc.fddts)) else None
-                mode, fw, fb = fddt_ptrs(fd, cfg)
-                ln, ln2 = lyr.self_attn_layer_norm, lyr.final_layer_norm
-                xln, mean, rstd = _e((rows, D), BF16, dev), _e((rows,), F32, dev), _e((rows,), F32, dev)
-                hp = _e((rows, D), F32, dev) if mode != ops.MODE_NONE else h
-                qkv, o, lse = _e((rows, 3 * D), BF16, dev), _e((rows, D), BF16, dev), _e((Bc, H, T), F32, dev)
-                h2, xln2 = _e((rows, D), F32, dev), _e((rows, D), BF16, dev)
-                mean2, rstd2 = _e((rows,), F32, dev), _e((rows,), F32, dev)
-                u, a, hn = _e((rows, F_), BF16, dev), _e((rows, F_), BF16, dev), _e((rows, D), F32, dev)
-                for st_, r, bsl in halves:
-                    with torch.cuda.stream(st_):
-                        ops.fddt_ln_fwd(h[r], rh, D, mode=mode, stno=stno[bsl.start * sstep:], stno_bstride=bstride, T=T, w=fw, b=fb,
-                                        h_out=hp[r] if mode != ops.MODE_NONE else None, ln_w=ln.weight.detach(),
-                                        ln_b=ln.bias.detach(), y_bf16=xln[r], mean=mean[r], rstd=rstd[r])
-                        linear_fwd(xln[r], w.att.qkv, rh, flags=L.EPI_SCALE_N, scale=Q_SCALE, scale_ncols=D, out=qkv[r])
-                        ops.attn_fwd(heads(qkv[r][:, :D], Bh, T, H), heads(qkv[r][:, D:2 * D], Bh, T, H), heads(qkv[r][:, 2 * D:], Bh, T, H),
-                                     heads(o[r], Bh, T, H), lse[bsl], q_log2=QK_LOG2)
-                        linear_fwd(o[r], w.att.o, rh, out_dtype=F32, residual=hp[r], out=h2[r])
-                        ops.fddt_ln_fwd(h2[r], rh, D, mode=ops.MODE_NONE, ln_w=ln2.weight.detach(), ln_b=ln2.bias.detach(), y_bf16=xln2[r],
-                                        mean=mean2[r], rstd=rstd2[r])
-                        linear_fwd(xln2[r], w.fc1, rh, gelu_aux=u[r], out=a[r])
-                        linear_fwd(a[r], w.fc2, rh, out_dtype=F32, residual=h2[r], out=hn[r])
+                S.split_from = i                                  # (the split backward covers the same layers: their saved buffers are full-batch, no SCB)
+                main_st, halves, _ = _fwd_parts(Bc, T, dev)       # fork: h (stem + initial FDDT, or the last speaker-communication layer) is complete
+            fd =enc.fddts[i] if (cfg.use_fddt and i < len(enc.fddts)) else None
+            mode, fw, fb = fddt_ptrs(fd, cfg)
+            use_scb = cfg.use_enrollments and cfg.scb_layers is not None and i < cfg.scb_layers
+            wfull = W.full[i] if (fd is not None and i < len(W.full)) else None
+            if need_grad and not use_scb and wfull is None:      # a plain layer's training forward: the shared chain, over all rows or per half
+                Ls.rows, Ls.B_after = rows, Bc
+                hn = layer_fwd_buffers(Ls, Bc, T, H, F_, own_hp=mode != ops.MODE_NONE)
+                for st_, r, bsl in halves or _one_part(Bc):
+                    with _on(st_):
+                        layer_rows_fwd(lyr, w, Ls, hn, r, bsl, bsl.stop - bsl.start, T, H, fddt=(mode, fw, fb, stno, bstride))
                 h = hn
-                Ls.rows, Ls.B_after, Ls.hp, Ls.xln, Ls.mean, Ls.rstd = rows, Bc, hp, xln, mean, rstd
-                Ls.qkv, Ls.o, Ls.lse, Ls.h2, Ls.xln2, Ls.mean2, Ls.rstd2, Ls.u, Ls.a = qkv, o, lse, h2, xln2, mean2, rstd2, u, a
                 S.layers.append(Ls)
                 continue
-            fd = enc.fddts[i] if (cfg.use_fddt and i < len(enc.fddts)) else None
-            mode, fw, fb = fddt_ptrs(fd, cfg)
             if fddt_done:
                 mode, fw, fb = ops.MODE_NONE, (None,) * 4, (None,) * 4
             nfd = enc.fddts[i + 1] if (fuse_next and i + 1 < len(enc.layers) and i + 1 < len(enc.fddts)) else None
             nmode, nfw, nfb = fddt_ptrs(nfd, cfg)
             fuse_here = nfd is not None and nmode == ops.MODE_DIAG and all(t is not None for t in nfw) and all(t is not None for t in nfb)
-            use_scb = cfg.use_enrollments and cfg.scb_layers is not None and i < cfg.scb_layers
-            wfull = W.full[i] if (fd is not None and i < len(W.full)) else None
-            if wfull is not None:                    # dense FDDT: its own GEMM + combine, the rest of the layer sees "no FDDT"
+            if wfull is not None:                   # dense FDDT: its own GEMM + combine, the rest of the layer sees "no FDDT"
                 h, Ls.full_hb = full_fddt_fwd(wfull, h, stno, bstride, rows, T, D)
                 Ls.h_in = h
                 mode, fw, fb = ops.MODE_NONE, (None,) * 4, (None,) * 4
@@ -805,16 +833,12 @@ class EncoderEngine:
         S.h_last, S.B_out, S.bstride_out = h, Bc, bstride
         enc_out, enc_bf = out if out is not None else (_e((rows, D), F32, dev), _e((rows, D), BF16, dev))
         S.meanf, S.rstdf = _e((rows,), F32, dev), _e((rows,), F32, dev)
-        if halves is not None:                           # the final LayerNorm per half too, then the join
-            for st_, r, bsl in halves:
-                with torch.cuda.stream(st_):
-                    ops.fddt_ln_fwd(h[r], rh, D, mode=ops.MODE_NONE, ln_w=enc.layer_norm.weight.detach(), ln_b=enc.layer_norm.bias.detach(),
-                                    y_bf16=enc_bf[r], y_f32=enc_out[r], mean=S.meanf[r], rstd=S.rstdf[r])
-            for st_, _, _ in halves[1:]:
-                main_st.wait_stream(st_)
-        else:
-            ops.fddt_ln_fwd(h, rows, D, mode=ops.MODE_NONE, ln_w=enc.layer_norm.weight.detach(), ln_b=enc.layer_norm.bias.detach(),
-                            y_bf16=enc_bf, y_f32=enc_out, mean=S.meanf, rstd=S.rstdf)
+        for st_, r, bsl in halves or _one_part(Bc):      # the final LayerNorm per half too, then the join
+            with _on(st_):
+                ops.fddt_ln_fwd(h[r], (bsl.stop - bsl.start) * T, D, mode=ops.MODE_NONE, ln_w=enc.layer_norm.weight.detach(),
+                                ln_b=enc.layer_norm.bias.detach(), y_bf16=enc_bf[r], y_f32=enc_out[r], mean=S.meanf[r], rstd=S.rstdf[r])
+        if halves is not None:
+            main_st.wait_stream(halves[1][0])
         S.enc_bf = enc_bf
         return enc_out.view(Bc, T, D), S
 
@@ -916,120 +940,66 @@ class EncoderEngine:
                 sync.done(name)
         hook("final_ln")
         start = nl - 1
-        if (SPLIT_BWD and SPLIT_FWD and getattr(S, "split_from", None) is not None and (sync is None or sync.role is None) and not WGRAD_SIDE_STREAM
+        if (SPLIT_BWD and SPLIT_FWD and getattr(S, "split_from", None) is not None and (sync is None or sync.role is None)
                 and S.B_out % 2 == 0 and _split_allowed() and self._split_bwd_fits(S, d_enc.device)):
             g, gb = self._backward_split(S, g, gb, G, hook)      # layers nl-1 .. split_from on two streams
             start = S.split_from - 1                             # (SE-DiCoW: the speaker-communication layers below follow on one stream)
-            if start < 0:
-                enter("stem")
-                self._stem_backward(S, g, G)
-                hook("stem")
-                return
         # Weight gradients are recorded per layer and run as ONE pooled launch (ops.TnGroup / dicow_gemm_tn_group) as soon as
         # the pool holds a tile for every CU: large-v3-turbo has 300 tiles per layer (one launch per layer), whisper-base 48
         # (all six layers in one launch at the end).  A layer's DP bucket is only handed over once its gradients have run.
         tng, pend, ncu, per_layer = ops.TnGroup(), [], ops.num_cus(dev), 0
-        side = wgrad_stream(dev) if (WGRAD_SIDE_STREAM and d_enc.is_cuda and not torch.cuda.is_current_stream_capturing()) else None
-
-        def run_wgrads(names):
-            if side is None or not tng.items:
-                tng.run()
-                for name in names:
-                    hook(name)
-                return
-            ready = torch.cuda.Event()
-            ready.record()                                    # every operand of the recorded problems has been enqueued
-            held = [t for it in tng.items for t in (it[0], it[1], it[2])] + ([G.flat] if G.flat.numel() > 1 else [])
-            with torch.cuda.stream(side):
-                side.wait_event(ready)
-                for t in held:                                # allocated on the compute stream, read here: no reuse before this stream is through
-                    if t is not None and t.is_cuda:
-                        t.record_stream(side)
-                tng.run()
-                for name in names:                            # (the DP bucket / the split-step event are recorded behind the launch, on this stream)
-                    hook(name)
         for i in range(start, -1, -1):
             n_before = len(tng.items)
             enter(f"layer{i}")
             lyr, w, Ls = enc.layers[i], W.layers[i], S.layers[i]
             rows, Bc = Ls.rows, Ls.B_after
-            # ---- FFN backward (the weight-gradient operands gb, d_u, g2b, d_qkv and the saved activations live on until tng.run())
-            linear_wgrad(gb, Ls.a, G.get(lyr.fc2.weight), rows, group=tng, param=lyr.fc2.weight)
-            d_u = linear_dgrad(gb, w.fc2, rows, aux=Ls.u, colsum_out=G.get(lyr.fc1.bias))     # fc1 bias grad = colsum(d_u), fused
-            linear_wgrad(d_u, Ls.xln2, G.get(lyr.fc1.weight), rows, group=tng, param=lyr.fc1.weight)
-            d_xln2 = linear_dgrad(d_u, w.fc1, rows)
-            g2 = _e((rows, D), F32, dev)
-            g2b = _e((rows, D), BF16, dev)
-            ln2 = lyr.final_layer_norm
-            ops.fddt_ln_bwd(Ls.h2, rows, D, mode=ops.MODE_NONE, ln_w=ln2.weight.detach(), mean=Ls.mean2, rstd=Ls.rstd2,
-                            d_y=d_xln2, g_res=g, g_out=g2, g_out_bf16=g2b, dln_w=G.get(ln2.weight), dln_b=G.get(ln2.bias),
-                            colsum_out=G.get(lyr.self_attn.out_proj.bias))
-            # ---- attention backward
-            att = lyr.self_attn
-            linear_wgrad(g2b, Ls.o, G.get(att.out_proj.weight), rows, group=tng, param=att.out_proj.weight)
-            d_o = linear_dgrad(g2b, w.att.o, rows)
-            d_qkv = _e((rows, 3 * D), BF16, dev)
-            delta = _e((2, Bc, H, T), F32, dev)
-            qkv = Ls.qkv
-            ops.attn_bwd(heads(qkv[:, :D], Bc, T, H), heads(qkv[:, D:2 * D], Bc, T, H), heads(qkv[:, 2 * D:], Bc, T, H),
-                         heads(Ls.o, Bc, T, H), heads(d_o, Bc, T, H), Ls.lse, delta, heads(d_qkv[:, :D], Bc, T, H),
-                         heads(d_qkv[:, D:2 * D], Bc, T, H), heads(d_qkv[:, 2 * D:], Bc, T, H), dq_scale=0.125, q_log2=QK_LOG2,
-                         dq_colsum=G.get(att.q_proj.bias), dv_colsum=G.get(att.v_proj.bias))   # q / v bias grads, fused
-            qkv_wgrad(d_qkv, Ls.xln, G.get(att.q_proj.weight), G.get(att.k_proj.weight), G.get(att.v_proj.weight), rows, D, group=tng,
-                      params=(att.q_proj.weight, att.k_proj.weight, att.v_proj.weight))
-            d_xln = linear_dgrad(d_qkv, w.att.qkv, rows)
-            # ---- LayerNorm1 (+ SCB) + FDDT backward; the column sum of the result is the previous fc2's bias grad
             fd = enc.fddts[i] if (cfg.use_fddt and i < len(enc.fddts)) else None
             mode, fw, fb = fddt_ptrs(fd, cfg)
-            dw = tuple(G.get(x) for x in fw)
-            db = tuple(G.get(x) for x in fb)
-            ln = lyr.self_attn_layer_norm
-            prev_b2 = G.get(enc.layers[i - 1].fc2.bias) if i > 0 else None
-            rows_in = Ls.B * T
-            g0 = _e((rows_in, D), F32, dev)
-            g0b = _e((rows_in, D), BF16, dev) if i > 0 else None
             wfull = W.full[i] if (fd is not None and i < len(W.full)) else None
-            if wfull is not None:                    # dense FDDT: LayerNorm (+ SCB) backward first, then its own backward
-                gf = _e((rows, D), F32, dev)
-                ops.fddt_ln_bwd(Ls.hp, rows, D, mode=ops.MODE_NONE, ln_w=ln.weight.detach(), mean=Ls.mean, rstd=Ls.rstd,
-                                d_y=d_xln, g_res=g2, g_out=gf, dln_w=G.get(ln.weight), dln_b=G.get(ln.bias))
-                if hasattr(Ls, "scb"):
-                    if getattr(Ls, "dropped", False):
-                        full = torch.zeros(rows_in, D, dtype=F32, device=dev)
-                        full.view(Ls.B // 2, 2, T, D)[:, 0].copy_(gf.view(Ls.B // 2, T, D))
-                        gf = full
-                    gf = self._scb_bwd(i, Ls.scb, gf, G, T)
-                g0 = full_fddt_bwd(fd, wfull, Ls.full_hb, gf, S.stno, Ls.bstride, G, rows_in, T, D)
-                if i > 0:
-                    g0b = ops.cast_bf16(g0)
-                    if prev_b2 is not None:
-                        ops.colsum_bf16(g0b, prev_b2)
-            elif not hasattr(Ls, "scb"):
-                ops.fddt_ln_bwd(Ls.h_in, rows, D, mode=mode, stno=S.stno, stno_bstride=Ls.bstride, T=T, w=fw, b=fb,
-                                ln_w=ln.weight.detach(), mean=Ls.mean, rstd=Ls.rstd, d_y=d_xln, g_res=g2, g_out=g0,
-                                g_out_bf16=g0b, dln_w=G.get(ln.weight), dln_b=G.get(ln.bias), dw=dw, db=db,
-                                colsum_out=prev_b2)
-            else:
+            plain = wfull is None and not hasattr(Ls, "scb")
+            prev_b2 = enc.layers[i - 1].fc2.bias if i > 0 else None       # the column sum of the layer's result is the previous fc2's bias grad
+            # (the weight-gradient operands gb, d_u, g2b, d_qkv and the saved activations live on in tng until it runs; the rest goes with bf)
+            bf = layer_bwd_buffers(rows, D, F_, dev, tail=plain, g0b=i > 0)
+            layer_rows_bwd(lyr, w, Ls, bf, slice(None), slice(0, Bc), Bc, T, H, g, gb, G.get, tail=plain,
+                           fddt=(mode, fw, fb, S.stno, Ls.bstride), prev_b2=prev_b2)
+            layer_wgrads(lyr, Ls, bf, gb, G, rows, group=tng)
+            if plain:
+                g, gb = bf.g0, bf.g0b
+            else:                                    # LayerNorm1 backward, then the speaker-communication block's and / or the FDDT's own
+                ln = lyr.self_attn_layer_norm
+                rows_in = Ls.B * T
                 gs = _e((rows, D), F32, dev)
                 ops.fddt_ln_bwd(Ls.hp, rows, D, mode=ops.MODE_NONE, ln_w=ln.weight.detach(), mean=Ls.mean, rstd=Ls.rstd,
-                                d_y=d_xln, g_res=g2, g_out=gs, dln_w=G.get(ln.weight), dln_b=G.get(ln.bias))
-                if getattr(Ls, "dropped", False):    # re-interleave: enrollment rows receive zero gradient
-                    full = torch.zeros(rows_in, D, dtype=F32, device=dev)
-                    full.view(Ls.B // 2, 2, T, D)[:, 0].copy_(gs.view(Ls.B // 2, T, D))
-                    gs = full
-                gin = self._scb_bwd(i, Ls.scb, gs, G, T)
-                ops.fddt_ln_bwd(Ls.h_in, rows_in, D, mode=mode, stno=S.stno, stno_bstride=Ls.bstride, T=T, w=fw, b=fb,
-                                g_res=gin, g_out=g0, g_out_bf16=g0b, dw=dw, db=db, colsum_out=prev_b2)
-            g, gb = g0, g0b
+                                d_y=bf.d_xln, g_res=bf.g2, g_out=gs, dln_w=G.get(ln.weight), dln_b=G.get(ln.bias))
+                if hasattr(Ls, "scb"):
+                    if getattr(Ls, "dropped", False):    # re-interleave: enrollment rows receive zero gradient
+                        full = torch.zeros(rows_in, D, dtype=F32, device=dev)
+                        full.view(Ls.B // 2, 2, T, D)[:, 0].copy_(gs.view(Ls.B // 2, T, D))
+                        gs = full
+                    gs = self._scb_bwd(i, Ls.scb, gs, G, T)
+                gb = None
+                if wfull is not None:                # dense FDDT
+                    g = full_fddt_bwd(fd, wfull, Ls.full_hb, gs, S.stno, Ls.bstride, G, rows_in, T, D)
+                    if i > 0:
+                        gb = ops.cast_bf16(g)
+                        if G.get(prev_b2) is not None:
+                            ops.colsum_bf16(gb, G.get(prev_b2))
+                else:
+                    g = _e((rows_in, D), F32, dev)
+                    gb = _e((rows_in, D), BF16, dev) if i > 0 else None
+                    ops.fddt_ln_bwd(Ls.h_in, rows_in, D, mode=mode, stno=S.stno, stno_bstride=Ls.bstride, T=T, w=fw, b=fb, g_res=gs,
+                                    g_out=g, g_out_bf16=gb, dw=tuple(G.get(x) for x in fw), db=tuple(G.get(x) for x in fb),
+                                    colsum_out=G.get(prev_b2))
+            del bf                                   # (before the next layer allocates its own: never two layers' buffers at once)
             pend.append(f"layer{i}")
             per_layer = max(per_layer, len(tng.items) - n_before)      # problems a layer records (4 with fused q/k/v, else 6)
             if i == 0 or tng.tiles() >= ncu or len(tng.items) + per_layer > L.TN_GROUP_MAX:
-                run_wgrads(pend)
+                tng.run()
+                for name in pend:
+                    hook(name)
                 pend = []
         enter("stem")
         self._stem_backward(S, g, G)
-        if side is not None:
-            torch.cuda.current_stream(dev).wait_stream(side)  # every dW is written before autograd / the optimizer / the "stem" bucket go on
         hook("stem")
 
     # -- the layers' backward as two half batches on two streams (the forward forked the same way: every saved buffer is full-batch)
@@ -1096,38 +1066,14 @@ class EncoderEngine:
         rows = Bc * T
         main_st, parts, Bh = _fwd_parts(Bc, T, dev)             # fork: g / gb (final LayerNorm backward) are complete
         side_st = parts[1][0]
-        rh = Bh * T
         sh, shget = self._shadow(G, dev)
         side_st.wait_stream(main_st)                             # (the zero fill of the stand-ins was enqueued behind the fork above)
-        keep, pending = [], None                                 # pending = (layer, its TnGroup, its stream's partner event)
-
-        third_st = wgrad_stream(dev) if SPLIT_BWD_WGRAD == "third" else None
-        deferred = []                                            # ("third": layers whose weight gradients run on the third stream, not yet settled)
-
-        def settle(item):                                        # ("third") one layer later still: the stand-in sums and the DP bucket behind the third stream's launch
-            i, ev_side, ev3 = item
-            main_st.wait_event(ev_side)
-            main_st.wait_event(ev3)
-            dst = [G.get(p) for p in sh.per[i]]
-            src = [sh.view[id(p)] for p, d in zip(sh.per[i], dst) if d is not None]
-            dst = [d for d in dst if d is not None]
-            if dst:
-                torch._foreach_add_(dst, src)
-            hook(f"layer{i}")
+        keep, pending = [], None                                 # pending = (layer, its TnGroup, the two halves' events)
+        alt = {"alt": True, "main": False}[SPLIT_BWD_WGRAD]      # (any other value: KeyError)
 
         def finish(item):                                        # a layer whose chain is enqueued on both streams: weight gradients, stand-in sums, DP bucket
             i, tg, ev_main, ev_side = item
-            if third_st is not None:                             # (experiment: every pooled launch on a third queue, neither chain ever carries one)
-                with torch.cuda.stream(third_st):
-                    third_st.wait_event(ev_main)
-                    third_st.wait_event(ev_side)
-                    tg.run()
-                    ev3 = third_st.record_event()
-                deferred.append((i, ev_side, ev3))
-                if len(deferred) > 1:
-                    settle(deferred.pop(0))
-                return
-            if SPLIT_BWD_WGRAD == "alt" and (i & 1):             # (experiment: odd layers' pooled launch on the side stream, to balance the streams)
+            if alt and (i & 1):                                  # odd layers' pooled launch on the side stream: the streams carry equal work
                 with torch.cuda.stream(side_st):
                     side_st.wait_event(ev_main)
                     tg.run()
@@ -1143,58 +1089,29 @@ class EncoderEngine:
                 torch._foreach_add_(dst, src)
             hook(f"layer{i}")
 
-        lo, sstep = S.split_from, S.split_sstep
+        lo = S.split_from
         for i in range(nl - 1, lo - 1, -1):
             lyr, w, Ls = enc.layers[i], W.layers[i], S.layers[i]
-            att, ln, ln2 = lyr.self_attn, lyr.self_attn_layer_norm, lyr.final_layer_norm
             fd = enc.fddts[i] if (cfg.use_fddt and i < len(enc.fddts)) else None
             mode, fw, fb = fddt_ptrs(fd, cfg)
             prev_b2 = enc.layers[i - 1].fc2.bias if i > 0 else None
-            d_u, d_xln2 = _e((rows, F_), BF16, dev), _e((rows, D), BF16, dev)
-            g2, g2b, d_o = _e((rows, D), F32, dev), _e((rows, D), BF16, dev), _e((rows, D), BF16, dev)
-            d_qkv, d_xln = _e((rows, 3 * D), BF16, dev), _e((rows, D), BF16, dev)
-            g0, g0b = _e((rows, D), F32, dev), (_e((rows, D), BF16, dev) if i > 0 else None)
-            keep += [d_u, d_xln2, g2, g2b, d_o, d_qkv, d_xln, g0, g0b, g, gb]
-            qkv = Ls.qkv
+            bf = layer_bwd_buffers(rows, D, F_, dev, g0b=i > 0)
+            keep += [bf, g, gb]
             evs = []
             for k, (st_, r, bsl) in enumerate(parts):
-                gg = G.get if k == 0 else shget
                 with torch.cuda.stream(st_):
-                    linear_dgrad(gb[r], w.fc2, rh, aux=Ls.u[r], colsum_out=gg(lyr.fc1.bias), out=d_u[r])
-                    linear_dgrad(d_u[r], w.fc1, rh, out=d_xln2[r])
-                    ops.fddt_ln_bwd(Ls.h2[r], rh, D, mode=ops.MODE_NONE, ln_w=ln2.weight.detach(), mean=Ls.mean2[r], rstd=Ls.rstd2[r],
-                                    d_y=d_xln2[r], g_res=g[r], g_out=g2[r], g_out_bf16=g2b[r], dln_w=gg(ln2.weight), dln_b=gg(ln2.bias),
-                                    colsum_out=gg(att.out_proj.bias))
-                    linear_dgrad(g2b[r], w.att.o, rh, out=d_o[r])
-                    delta = _e((2, Bh, H, T), F32, dev)
-                    ops.attn_bwd(heads(qkv[r][:, :D], Bh, T, H), heads(qkv[r][:, D:2 * D], Bh, T, H), heads(qkv[r][:, 2 * D:], Bh, T, H),
-                                 heads(Ls.o[r], Bh, T, H), heads(d_o[r], Bh, T, H), Ls.lse[bsl], delta, heads(d_qkv[r][:, :D], Bh, T, H),
-                                 heads(d_qkv[r][:, D:2 * D], Bh, T, H), heads(d_qkv[r][:, 2 * D:], Bh, T, H), dq_scale=0.125, q_log2=QK_LOG2,
-                                 dq_colsum=gg(att.q_proj.bias), dv_colsum=gg(att.v_proj.bias))
-                    linear_dgrad(d_qkv[r], w.att.qkv, rh, out=d_xln[r])
-                    ops.fddt_ln_bwd(Ls.h_in[r], rh, D, mode=mode, stno=S.stno[bsl.start * sstep:], stno_bstride=Ls.bstride, T=T, w=fw, b=fb,
-                                    ln_w=ln.weight.detach(), mean=Ls.mean[r], rstd=Ls.rstd[r], d_y=d_xln[r], g_res=g2[r], g_out=g0[r],
-                                    g_out_bf16=g0b[r] if g0b is not None else None, dln_w=gg(ln.weight), dln_b=gg(ln.bias),
-                                    dw=tuple(gg(x) for x in fw), db=tuple(gg(x) for x in fb), colsum_out=gg(prev_b2))
-                    keep.append(delta)
+                    keep.append(layer_rows_bwd(lyr, w, Ls, bf, r, bsl, Bh, T, H, g, gb, G.get if k == 0 else shget,
+                                               fddt=(mode, fw, fb, S.stno, Ls.bstride), prev_b2=prev_b2))
                     evs.append(st_.record_event())
             # the layer's weight gradients: recorded now (first-writer flags consumed in layer order), launched one layer late
             tg = ops.TnGroup()
-            linear_wgrad(gb, Ls.a, G.get(lyr.fc2.weight), rows, group=tg, param=lyr.fc2.weight)
-            linear_wgrad(d_u, Ls.xln2, G.get(lyr.fc1.weight), rows, group=tg, param=lyr.fc1.weight)
-            linear_wgrad(g2b, Ls.o, G.get(att.out_proj.weight), rows, group=tg, param=att.out_proj.weight)
-            qkv_wgrad(d_qkv, Ls.xln, G.get(att.q_proj.weight), G.get(att.k_proj.weight), G.get(att.v_proj.weight), rows, D, group=tg,
-                      params=(att.q_proj.weight, att.k_proj.weight, att.v_proj.weight))
+            layer_wgrads(lyr, Ls, bf, gb, G, rows, group=tg)
             if pending is not None:
                 finish(pending)
             pending = (i, tg, evs[0], evs[1])
-            g, gb = g0, g0b
+            g, gb = bf.g0, bf.g0b
         finish(pending)
-        while deferred:
-            settle(deferred.pop(0))
         main_st.wait_stream(side_st)
-        if third_st is not None:
-            main_st.wait_stream(third_st)
         if lo > 0:                                               # layer lo's row kernel reduced into layer lo-1's fc2 bias: half 1's share joins it here
             pb = enc.layers[lo - 1].fc2.bias
             if G.get(pb) is not None:
@@ -1340,11 +1257,11 @@ class DecoderEngine:
         if split:
             main_st, parts, Bh = _fwd_parts(B, 1, dev)       # (row slices in units of sequences)
         else:
-            main_st, parts, Bh = None, ((None, slice(0, B), slice(0, B)),), B
+            main_st, parts, Bh = None, _one_part(B), B
         S.parts = []
         for st_, _, bsl in parts:
             rq, re = slice(bsl.start * Lq, bsl.stop * Lq), slice(bsl.start * T, bsl.stop * T)
-            with (torch.cuda.stream(st_) if st_ is not None else contextlib.nullcontext()):
+            with _on(st_):
                 hl, layers = self._layers_fwd(enc_bf[re], Bh, T, Lq, h[rq])
                 ops.fddt_ln_fwd(hl, Bh * Lq, D, ln_w=dec.layer_norm.weight.detach(), ln_b=dec.layer_norm.bias.detach(), y_bf16=S.xf[rq],
                                 mean=S.mf[rq], rstd=S.rf[rq])
@@ -1486,7 +1403,7 @@ class DecoderEngine:
                 P.st.wait_stream(main_st)                # fork: d_xf and the zeroed d_enc are complete
         for P in S.parts:
             rq, re, rows_p = P.rq, P.re, P.B * Lq
-            with (torch.cuda.stream(P.st) if split else contextlib.nullcontext()):
+            with _on(P.st):
                 gb = _e((rows_p, D), BF16, dev)
                 ops.fddt_ln_bwd(P.h_last, rows_p, D, ln_w=dec.layer_norm.weight.detach(), mean=S.mf[rq], rstd=S.rf[rq], d_y=d_xf[rq], g_out=g[rq],
                                 g_out_bf16=gb, dln_w=G.get(dec.layer_norm.weight), dln_b=G.get(dec.layer_norm.bias),

@@ -505,8 +505,6 @@ class GradReducer:
         return ms
 
 
-_SPLIT_NOWAIT = os.environ.get("DICOW_SPLIT_NOWAIT") == "1"       # timing experiments only: the halves' gradient sums race
-_SPLIT_LEAD_FIRST = os.environ.get("DICOW_SPLIT_LEAD_FIRST", "1") == "1"
 _SPLIT_GROUP = int(os.environ.get("DICOW_SPLIT_GROUP", "2"))     # encoder layers per cross-stream wait
 
 
@@ -536,7 +534,7 @@ class SplitSync:
         return f"layer{i - i % self.group}"
 
     def enter(self, name):
-        if self.role == "follow" and not _SPLIT_NOWAIT:
+        if self.role == "follow":
             gate = self._gate(name)
             if gate == self.free_until:                 # already waited for this group's lowest layer
                 return
@@ -698,8 +696,7 @@ class TrainStep:
         model, enc, sync = self.model, self.model.model.encoder, self._split_sync
         cur = torch.cuda.current_stream()
         if self._split_side is None:                    # (priority streams get hardware queues of their own: profiles/r06_streams.txt)
-            pf, pl = (int(x) for x in os.environ.get("DICOW_SPLIT_PRIO", "-1,-1").split(","))
-            self._split_side = (torch.cuda.Stream(priority=pf), torch.cuda.Stream(priority=pl))
+            self._split_side = (torch.cuda.Stream(priority=-1), torch.cuda.Stream(priority=-1))
         s_f, s_l = self._split_side
         hb = batch["labels"].shape[0] // 2
         halves = [{k: (v[i * hb:(i + 1) * hb] if torch.is_tensor(v) and v.dim() > 0 else v) for k, v in batch.items()} for i in (0, 1)]
@@ -718,7 +715,7 @@ class TrainStep:
         try:
             with tracing.range("forward"):
                 outs = [None, None]
-                for i, st in (((1, s_l), (0, s_f)) if _SPLIT_LEAD_FIRST else ((0, s_f), (1, s_l))):     # the leader's forward is enqueued first: it stays ahead
+                for i, st in ((1, s_l), (0, s_f)):      # the leader's forward is enqueued first: it stays ahead
                     st.wait_stream(cur)
                     with torch.cuda.stream(st):
                         outs[i] = model(**halves[i])
