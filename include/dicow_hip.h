@@ -719,6 +719,51 @@ int dicow_diar_score(const int64_t* bounds, int64_t n_bounds, const uint64_t* ac
                      int64_t n_unscored, const int64_t* problems, int n_problems, int chunk, int64_t* out, void* ws, int64_t ws_bytes,
                      void* stream);
 
+/* Cutting hallucinated repeats from hypotheses before they are scored (ABI 7, additive): where a decoded segment has to end so that a
+ * looping hallucination ("thank you thank you ...", "a b a b ...") is cut at its first repeat -- the reference's
+ * truncate_at_repeating_ngram (src/data/postprocess.py:18-74), which process_session (src/utils/evaluation.py:150-176) applies to every
+ * segment before calc_wer sees it -- for n independent segments in one call.
+ * ids / fold: device int32 [n_words]; table: a HOST int64 [n][2] table of (start, len).  Segment s is the W = len words at [start, start + W):
+ *   id[0..W)    the exact ids: equal iff the words are equal strings,
+ *   fold[0..W)  the folded ids: equal iff the words' lower-cased forms are equal.
+ * Parameters min_n >= 1, max_n, min_words, u = unigram_min_repeat >= 1, r = repeat_threshold >= 0.  THE DEFINITION:
+ *   run(i)   = the length of the maximal run fold[i] == fold[i + 1] == ... that starts at i;
+ *   occ_n(i) = the number of j in [0, W - n] with id[j + k] == id[i + k] for all k < n (j == i counts, overlapping occurrences count);
+ *   cnt_n(i) = 0 if fold[i .. i + n) are all equal (such an n-gram is never counted), else occ_n(i), for max(2, min_n) <= n <= max_n and
+ *              i <= W - n; cnt_n = 0 for every other n.
+ *   keep     = W if W < min_words; otherwise the minimum of
+ *                W,
+ *                i0 + 1 with i0 the smallest i <= W - u that has run(i) >= u        (this term exists only if min_n == 1),
+ *                i + n over all (n, i) with cnt_n(i) > r.
+ * So the counts are case-sensitive, the degenerate test and the unigram run are not, a count equal to r does not cut, and an n-gram never
+ * spans two segments.  The reference's ngram_length influences nothing but the default of max_n.
+ *   reason[s] = (n, i, count): what attained keep.  (0, 0, 0) if nothing was cut (keep == W); (1, i0, run(i0)) for the unigram rule, the
+ *   full run, not capped; otherwise (n, i, cnt_n(i)).  THE TIE RULE among the candidates that attain the minimum is the project's own (the
+ *   reference reports no reason): the unigram rule wins, then the smallest n.
+ * Outputs, device buffers, one writer per element, no atomics: keep int32 [n]; reason int32 [n][3], or NULL.
+ * Launches: the host cuts every segment that can be cut (W >= min_words, some n in range) into work items of R rows i; a workgroup of R
+ * lanes keeps each row's window id[i .. i + max_n) in registers, streams the segment's words through LDS in chunks of C and counts for
+ * every n at once the j whose match is at least n words long; it min-reduces one packed key (keep, n, count) per item.  A second launch of
+ * one wave per segment folds the items, finds i0 from the run boundaries and writes keep and reason.  plan: 0 = the library's choice for the
+ * call, or 1 .. DICOW_NGRAM_PLANS for (R, C) = (64, 256), (64, 1024), (256, 256), (256, 1024) (tests, measurements); a segment's result
+ * depends neither on the plan nor on the other segments.  One copy (the tables, into ws, on the stream) and two launches, no host read:
+ * the call can be captured into a graph.
+ * ws: dicow_ngram_repeats_ws_bytes(table, n, plan) bytes, 16-byte aligned, at most DICOW_NGRAM_MAX_WS_BYTES: DICOW_NGRAM_SEG_BYTES a
+ * segment and DICOW_NGRAM_ITEM_BYTES a possible work item (ceil((W - 1) / R) a segment), rounded up to 16, and 8 bytes a possible item.
+ * Checked on the host before anything is launched (-1, dicow_last_error() names the limit): W in [0, DICOW_NGRAM_MAX_WORDS]; plan; the
+ * workspace limit; the spans inside n_words; min_n >= 1, max_n <= DICOW_NGRAM_MAX_N, u >= 1, r >= 0; pointers and their alignment;
+ * ws_bytes.  dicow_ngram_repeats_ws_bytes checks the lengths, the plan and the limit alone.  n == 0 launches nothing. */
+#define DICOW_NGRAM_MAX_N 16
+#define DICOW_NGRAM_MAX_WORDS 65535
+#define DICOW_NGRAM_PLANS 4
+#define DICOW_NGRAM_MAX_WS_BYTES 1073741824LL
+#define DICOW_NGRAM_SEG_BYTES 24
+#define DICOW_NGRAM_ITEM_BYTES 8
+int64_t dicow_ngram_repeats_ws_bytes(const int64_t* table, int n, int plan);
+int dicow_ngram_repeats(const int32_t* ids, const int32_t* fold, int64_t n_words, const int64_t* table, int n, int min_n, int max_n,
+                        int min_words, int unigram_min_repeat, int repeat_threshold, int32_t* keep, int32_t* reason, int plan, void* ws,
+                        int64_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ batch augmentation
  * The collator's training-time augmentations (reference src/data/collators.py:189-214), applied to the batch where it
  * already lives (HBM).  The random decisions are drawn on the host from the torch CPU generator in the reference's

@@ -91,6 +91,10 @@ ORC_MAX_STREAMS, ORC_K, ORC_MAX_WORDS, ORC_MAX_STATES, ORC_MAX_WS_BYTES, ORC_DES
 DIAR_SCORE_CHUNK, DIAR_SCORE_ROW, DIAR_SCORE_OUT_WORDS, DIAR_SCORE_DESC_BYTES = 256, 12, 4232, 120
 DIAR_SCORE_MAX_E, DIAR_SCORE_MAX_TICK, DIAR_SCORE_MAX_WS_BYTES = 1 << 24, 1 << 40, 1 << 32
 
+# DICOW_NGRAM_*: dicow_ngram_repeats's longest n-gram, longest segment, number of plans, workspace limit and table bytes per segment / item
+NGRAM_MAX_N, NGRAM_MAX_WORDS, NGRAM_PLANS, NGRAM_MAX_WS_BYTES, NGRAM_SEG_BYTES, NGRAM_ITEM_BYTES = 16, 65535, 4, 1 << 30, 24, 8
+NGRAM_PLAN_TILES = {1: (64, 256), 2: (64, 1024), 3: (256, 256), 4: (256, 1024)}   # plan -> (R rows a workgroup, C words a chunk)
+
 LORA_MAX_R, LORA_MAX_SEG = 192, 24
 LORA_BLOCK, LORA_OUT_F32, LORA_GELU, LORA_MUL_AUX = 1, 2, 4, 8
 
@@ -218,6 +222,7 @@ _SIGS = {
     "dicow_edit_alignment": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_i, c_i, c_vp, c_i64, c_vp],
     "dicow_orc_distance": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "dicow_diar_score": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_vp, c_vp, c_i64, c_vp],
+    "dicow_ngram_repeats": [c_vp, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp, c_i, c_vp, c_i64, c_vp],
     "dicow_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
     "dicow_fabric_emulate": [c_vp, c_i64, c_d, c_i, c_i, c_vp],
     "dicow_adamw_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_i, c_vp, c_f, c_vp],
@@ -306,6 +311,7 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
     "dicow_ctc_align_ws_bytes": [c_vp, c_i],
     "dicow_orc_distance_ws_bytes": [c_vp, c_i, c_vp, c_vp, c_i],
     "dicow_diar_score_ws_bytes": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i],
+    "dicow_ngram_repeats_ws_bytes": [c_vp, c_i, c_i],
 }
 
 
