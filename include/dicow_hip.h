@@ -246,7 +246,10 @@ int dicow_gemm_tn_group(const dicow_gemm_tn_group_args* a, void* stream);
  * Flash-style softmax(Q K^T) V with head_dim 64, scaling 1.0 (q is pre-scaled by the projection epilogue,
  * HF:modeling_whisper.py:309,337-351).  Dense (encoder 1500x1500, SE enrollment cross-attention
  * layers.py:152-157), causal (decoder self-attention) and rectangular (decoder cross-attention) shapes.
- * q/k/v/o are bf16 with explicit strides (elements): element (b, t, h, d) at  base + b*bs + t*rs + h*64 + d. */
+ * q/k/v/o are bf16 with explicit strides (elements): element (b, t, h, d) at  base + b*bs + t*rs + h*64 + d.
+ * Batch strides and the q / o row strides are 64-bit throughout.  K and V tiles are fetched with 32-bit byte offsets from the
+ * (batch, head) base, so their row strides obey  (max(Lk, 65) - 1) * rs * 2 + 128 < 2^32;  a call past that limit returns
+ * DICOW_ERR_INVALID before any launch (dicow_attn_fwd_route: NULL). */
 typedef struct {
     const void* q; const void* k; const void* v; void* o;
     float* lse;                                     /* [B,H,Lq] natural-log-sum-exp, saved for backward */
@@ -365,6 +368,9 @@ typedef struct {
     int fused_mode;                                 /* 0: the library decides (above); 1: the fused kernel for EVERY dense problem it can
                                                        address (B*H <= 1000), whatever its size -- how the tests reach its edge cases */
 } dicow_attn_bwd_args;
+/* Strides: batch strides and the o / dq / dk / dv row strides are 64-bit throughout.  The K, V, Q and dO tiles are fetched with 32-bit
+ * byte offsets from the (batch, head) base:  (max(L, 65) - 1) * rs * 2 + 128 < 2^32  for k_rs, v_rs (L = Lk) and q_rs, do_rs (L = Lq);
+ * a call past that limit returns DICOW_ERR_INVALID before any launch (dicow_attn_bwd_route: NULL). */
 int dicow_attn_bwd(const dicow_attn_bwd_args* a, void* stream);
 int64_t dicow_attn_bwd_colsum_ws_bytes(int B, int H, int Lq, int Lk);
 int64_t dicow_attn_bwd_fused_ws_bytes(int B, int H, int Lq, int Lk);

@@ -285,6 +285,75 @@ def test_attention_routes_host_logic():
         assert query(None) is None
 
 
+def _attn_rs_limit(L):
+    """The largest row stride (elements, a multiple of 8) attention's 32-bit tile offsets can address: (max(L, 65) - 1) * rs * 2 + 128 <
+    2^32 (attention.hip check_tile_span: num_records of make_tile_src, the lane and tile offsets of stage_tile / stage_tile_x)."""
+    return ((1 << 32) - 129) // (2 * (max(L, 65) - 1)) // 8 * 8
+
+
+def test_attention_row_stride_limit_host_logic():
+    """K and V (forward and backward), Q and dO (backward) are fetched with 32-bit byte offsets from the (batch, head) base: at the
+    largest 8-multiple row stride inside the limit the route queries name a route, one step (+8) past it they answer NULL, and the
+    other operands' row strides (q and o in the forward; o, dq, dk, dv in the backward) and every batch stride have no such limit."""
+    import ctypes as C
+    from ts_asr_whisper_amd import _lib
+    lib = _lib.lib()
+    for L in (100, 140, 260, 1500):
+        rs = _attn_rs_limit(L)
+        assert (L - 1) * rs * 2 + 128 < 1 << 32 <= (L - 1) * (rs + 8) * 2 + 128          # for L >= 65 this IS the span of the operand
+    assert 64 * _attn_rs_limit(2) * 2 + 128 < 1 << 32 <= 64 * (_attn_rs_limit(2) + 8) * 2 + 128      # short operands: 65 rows count
+    for Lq, Lk in ((100, 100), (140, 260), (2, 2)):
+        for name, L in (("k_rs", Lk), ("v_rs", Lk)):
+            rs = _attn_rs_limit(L)
+            assert lib.dicow_attn_fwd_route(C.byref(_attn_fwd_args(Lq=Lq, Lk=Lk, **{name: rs}))) == b"occ4", (name, Lq, Lk)
+            assert lib.dicow_attn_fwd_route(C.byref(_attn_fwd_args(Lq=Lq, Lk=Lk, **{name: rs + 8}))) is None, (name, Lq, Lk)
+            assert b"2^32" in lib.dicow_last_error() and name[0].encode() in lib.dicow_last_error()
+        for name in ("q_rs", "o_rs", "q_bs", "k_bs", "v_bs", "o_bs"):
+            assert lib.dicow_attn_fwd_route(C.byref(_attn_fwd_args(Lq=Lq, Lk=Lk, **{name: 1 << 40}))) == b"occ4", name
+        for fm, route in ((0, b"dq_dkv"), (1, b"fused")):
+            kw = dict(B=2, H=2, Lq=Lq, Lk=Lk, fused_mode=fm)
+            for name, L in (("k_rs", Lk), ("v_rs", Lk), ("q_rs", Lq), ("do_rs", Lq)):
+                rs = _attn_rs_limit(L)
+                assert lib.dicow_attn_bwd_route(C.byref(_attn_bwd_args(**kw, **{name: rs}))) == route, (name, Lq, Lk)
+                assert lib.dicow_attn_bwd_route(C.byref(_attn_bwd_args(**kw, **{name: rs + 8}))) is None, (name, Lq, Lk)
+                assert b"2^32" in lib.dicow_last_error()
+            for name in ("o_rs", "dq_rs", "dk_rs", "dv_rs", "q_bs", "k_bs", "v_bs", "o_bs", "do_bs", "dq_bs", "dk_bs", "dv_bs"):
+                assert lib.dicow_attn_bwd_route(C.byref(_attn_bwd_args(**kw, **{name: 1 << 40}))) == route, name
+
+
+def test_far_view_helpers_on_the_host():
+    """tests/util's far-offset helpers without a GPU: the tall-stride recipe puts rows on both sides of the mark and finds a row that
+    straddles it; far_view keeps the front pad; the stray count flags one stray byte, an overlap and a changed input."""
+    from tests.util import Arena, far_view, tall_ld
+    for rows, cols, isz, align in ((300, 128, 2, 8), (132, 128, 2, 8), (44, 1000, 2, 8), (1000, 500, 4, 4), (16, 1284, 2, 4)):
+        ld, r = tall_ld(rows, cols, isz, align)
+        assert ld % align == 0 and ld >= cols and (rows - 1) * ld * isz >= 1 << 32 and (rows // 2) * ld * isz < 1 << 32
+        assert r is not None and r * ld * isz < 1 << 32 < (r * ld + cols) * isz
+    ld, r = tall_ld(40, 16, 2, 8, mark=1 << 16)
+    arena = Arena(1 << 20, device="cpu")
+    vals = torch.randn(40, 16).bfloat16()
+    v = far_view(arena, (40, 16), torch.bfloat16, (ld, 1), values=vals, name="x")
+    span = (39 * ld + 16) * 2
+    assert span > 1 << 16 and v.data_ptr() - arena.buf.data_ptr() >= span and torch.equal(v, vals)
+    out = far_view(arena, (40, 16), torch.float32, (ld, 1), name="y", output=True)
+    assert arena.check() == 40 * 16
+    out.copy_(torch.randn(40, 16))
+    assert arena.check() == 3 * 40 * 16
+    arena.buf[6] = 0
+    with pytest.raises(AssertionError, match="1 stray"):
+        arena.check()
+    arena.buf[6] = 0xC1
+    far_view(arena, (40, 16), torch.bfloat16, (ld, 1), values=vals, base_bytes=v.data_ptr() - arena.buf.data_ptr(), name="overlap")
+    with pytest.raises(AssertionError, match="stray"):
+        arena.check()
+    arena.inputs.pop()
+    v[3, 3] = 2.0
+    with pytest.raises(AssertionError, match="input operand was overwritten"):
+        arena.check()
+    with pytest.raises(AssertionError, match="front pad"):
+        far_view(arena, (40, 16), torch.bfloat16, (ld, 1), values=vals, base_bytes=256, name="no pad")
+
+
 def test_attn_bwd_fused_eligible_matches_the_former_python_rule():
     """dicow_attn_bwd_fused_eligible against the predicate that stood in ops.attn_bwd (moved here verbatim: `want` is True or "force").
     The two may differ only where the hand-off tiles would reach 2^32 bytes: the library never ran those fused, and ops.attn_bwd

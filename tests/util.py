@@ -299,3 +299,130 @@ def poisoned(t, ld, device="cuda", *, strides=None, offset=0, span_rows=None, ki
     view = buf.as_strided(shape, strides, lead + offset)
     view.copy_(t.to(device))
     return view
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Far-offset helpers (tests/test_gpu_far_offsets.py): operands whose elements lie more than 2^31 / 2^32 bytes from their base
+# pointer, as strided views into ONE device arena that holds the NaN sentinel of the guards everywhere else.
+MARK31, MARK32 = 1 << 31, 1 << 32
+FAR_FRONT_CAP = 8 << 30      # front pad of a far view: its own span, capped here (see far_view)
+ARENA_MAX_BYTES = 20 << 30
+_SCAN_WORDS = 1 << 28        # 16-bit words per chunk of the device scans (512 MiB, no full-size mask)
+
+
+def _word_checksum(t):
+    """Sum of the 16-bit words of a (compact) tensor as integers, chunk by chunk: cheap evidence that an input was not overwritten."""
+    w = t.contiguous().view(torch.int16).reshape(-1)
+    return sum(int(w[s:s + _SCAN_WORDS].sum(dtype=torch.int64)) for s in range(0, w.numel(), _SCAN_WORDS))
+
+
+def _nonsentinel_words(t):
+    """16-bit words of a (compact) tensor that differ from the sentinel."""
+    w = t.contiguous().view(torch.int16).reshape(-1)
+    return sum(int((w[s:s + _SCAN_WORDS] != SENTINEL16).sum()) for s in range(0, w.numel(), _SCAN_WORDS))
+
+
+class Arena:
+    """One uint8 device allocation, filled with the sentinel by reset(); far_view() places logical operands in it.  check() counts
+    the 16-bit words of the WHOLE arena that are not the sentinel, chunk by chunk on the device, and compares the count with the
+    words of the placed views themselves (inputs as placed, outputs as they are now; a logical word whose bits happen to equal
+    the sentinel counts on neither side): any store outside the logical regions makes the counts differ, and so do two views
+    that overlap.  Inputs must also still hold the bits they were given."""
+
+    def __init__(self, nbytes, device="cuda"):
+        assert nbytes % 4096 == 0 and nbytes <= ARENA_MAX_BYTES
+        self.nbytes, self.buf = nbytes, torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.reset()
+
+    def reset(self):
+        self.buf.view(torch.int16).fill_(SENTINEL16)
+        self.inputs, self.outputs, self.used = [], [], 0
+
+    def count_nonsentinel(self):
+        return _nonsentinel_words(self.buf)
+
+    def check(self):
+        if self.buf.is_cuda:
+            torch.cuda.synchronize()
+        for name, view, vals, _ in self.inputs:
+            same = torch.equal(view, vals) if torch.is_tensor(vals) else _word_checksum(view) == vals       # (filled in place: a checksum)
+            assert same, f"{name}: an input operand was overwritten"
+        want = sum(n for *_, n in self.inputs) + sum(_nonsentinel_words(v) for _, v in self.outputs)
+        got = self.count_nonsentinel()
+        assert got == want, f"arena holds {got} non-sentinel words, the logical operands {want}: {got - want} stray (or missing) words"
+        return got
+
+
+def far_arena_fixture(nbytes, headroom):
+    """The module-scoped arena fixture of a test file (import the returned function under the name the tests use): ONE allocation of
+    `nbytes`, made once; skips when the device has less than nbytes + headroom (the compact operands and references) free."""
+    import pytest
+
+    @pytest.fixture(scope="module")
+    def far_arena_module():
+        if not torch.cuda.is_available():
+            pytest.skip("no GPU")
+        need = nbytes + headroom
+        if torch.cuda.mem_get_info()[0] < need:
+            pytest.skip(f"needs {-(-need >> 30)} GiB of free device memory")
+        arena = Arena(nbytes)
+        yield arena
+        arena.buf = None
+
+    return far_arena_module
+
+
+def _ceil_to(x, a):
+    return -(-x // a) * a
+
+
+def tall_ld(rows, row_elems, itemsize, align_elems=8, mark=MARK32, straddle=True):
+    """Tall-stride recipe: a leading dimension (elements, a multiple of align_elems) near mark / (rows - 2) bytes, so that the rows
+    around rows / 2 begin near mark / 2 and the last row begins past the mark.  Among the rows of the upper half the one is looked
+    for that can BEGIN less than one row length below the mark, so that its elements straddle it (the carry inside a row).
+    Returns (ld, straddling row or None)."""
+    assert rows >= 4
+    ab, rb = align_elems * itemsize, row_elems * itemsize
+    for r in range(rows - 2, rows // 2 if straddle else rows - 2, -1):      # (straddle=False: the plain recipe, the smallest span)
+        ldb = mark // r // ab * ab
+        below = mark - r * ldb                                # row r begins `below` bytes under the mark
+        if 0 < below < rb and ldb >= rb:
+            assert (rows - 1) * ldb >= mark and r * ldb < mark < r * ldb + rb
+            return ldb // itemsize, r
+    ldb = _ceil_to(-(-mark // (rows - 2)), ab)
+    assert (rows - 1) * ldb >= mark and ldb >= rb
+    return ldb // itemsize, None
+
+
+def far_view(arena, shape, dtype, strides, *, values=None, base_bytes=None, name="far", output=False, fill=None):
+    """A strided view (strides in elements, last one 1) of the arena with the logical `values` written into it (outputs: nothing is
+    written, the region keeps the sentinel; fill(view): an input too large to exist twice is generated in place).  base_bytes: where in the arena the view begins (default: after everything placed so
+    far).  FRONT PAD, asserted here: the base lies at least min(span, 8 GiB) into the arena, so an offset truncated to 32 bits, taken
+    as a signed 32-bit byte count or wrapped as a 32-bit ELEMENT index (2^32 elements = 8 GiB of bf16) still lands inside the
+    arena -- a wrapped read sees the sentinel, a wrapped write lands where check() looks -- instead of leaving the allocation."""
+    isz = torch.empty(0, dtype=dtype).element_size()
+    shape, strides = tuple(int(s) for s in shape), tuple(int(s) for s in strides)
+    assert len(shape) == len(strides) and strides[-1] == 1 and all(s >= 0 for s in strides)
+    span = (sum((n - 1) * s for n, s in zip(shape, strides)) + 1) * isz
+    front = min(span, FAR_FRONT_CAP)
+    base = _ceil_to(max(arena.used, front), 256) if base_bytes is None else int(base_bytes)
+    assert base % 256 == 0 and base >= front, (name, "front pad", base, front)
+    assert base + span <= arena.nbytes, (name, "the arena is too small", base + span, arena.nbytes)
+    # the wrapped images of every offset o < span stay inside [0, base + span): o mod 2^32 (o - 2^32 only where o >= 2^32), o as a
+    # signed 32-bit byte count (o - 2^32 for o in [2^31, 2^32): >= -2^31), o / isz as a signed 32-bit element index (only where
+    # o >= 2^31 isz, and then o - 2^32 isz >= -2^31 isz)
+    assert base >= min(span, MARK31) and (span < MARK31 * isz or base >= MARK31 * isz)
+    typed = arena.buf[base:base + span].view(dtype)
+    view = typed.as_strided(shape, strides, typed.storage_offset())
+    arena.used = max(arena.used, base + span)
+    if output:
+        assert values is None and fill is None
+        arena.outputs.append((name, view))
+    elif fill is not None:
+        fill(view)
+        arena.inputs.append((name, view, _word_checksum(view), _nonsentinel_words(view)))
+    else:
+        vals = values.to(device=arena.buf.device, dtype=dtype).contiguous()
+        view.copy_(vals)
+        arena.inputs.append((name, view, vals, _nonsentinel_words(vals)))
+    return view

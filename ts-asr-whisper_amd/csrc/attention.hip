@@ -36,29 +36,29 @@ __device__ __forceinline__ int vswz(int row, int c) { return row * 128 + ((c ^ (
 // instructions with a SCALAR row offset and no VALU address arithmetic -- plain VALU instructions share the SIMD's issue
 // port with the MFMAs (tools/probe_overlap.hip), so per-tile pointer math was ~20 % of the loop's VALU work.
 enum { SWZ_K = 0, SWZ_V = 1, SWZ_U = 2 };
-struct tile_src_t { __amdgpu_buffer_rsrc_t rs; unsigned vo[2]; int row_bytes; };
+struct tile_src_t { __amdgpu_buffer_rsrc_t rs; unsigned vo[2]; unsigned row_bytes; };      // (all offsets unsigned: they pass 2^31, see check_tile_span)
 __device__ __forceinline__ int rev3(int x);
 template <int SWZ, int NI = 2>      // NI = DMA instructions per wave and tile: 2 when four waves share a tile, 1 when eight do
 __device__ __forceinline__ tile_src_t make_tile_src(const unsigned short* base, int64_t rs, int nrows, int wave, int lane) {
     tile_src_t t;
     t.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(base), 0,
                                              (unsigned)(((int64_t)(nrows - 1) * rs + HD) * 2), 0x00020000);
-    t.row_bytes = (int)(rs * 2);
+    t.row_bytes = (unsigned)(rs * 2);
     const int rr = lane >> 3, p = lane & 7;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int row = (wave * NI + i) * 8 + rr;
         const int c = SWZ == SWZ_V ? (p ^ (((row >> 1) & 1) << 2)) : SWZ == SWZ_K ? (p ^ ((row >> 1) & 7)) : (p ^ rev3((row >> 1) & 7));
-        t.vo[i] = (unsigned)(row * (int)(rs * 2) + c * 16);
+        t.vo[i] = (unsigned)row * t.row_bytes + (unsigned)(c * 16);
     }
     return t;
 }
 template <int NI = 2>
 __device__ __forceinline__ void stage_tile(const tile_src_t& t, int row0, char* lds, int wave) {
-    const int so = row0 * t.row_bytes;
+    const unsigned so = (unsigned)row0 * t.row_bytes;
 #pragma unroll
     for (int i = 0; i < NI; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(t.rs, (lds_void_t*)(lds + (wave * NI + i) * 1024), 16, t.vo[i], so, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(t.rs, (lds_void_t*)(lds + (wave * NI + i) * 1024), 16, t.vo[i], (int)so, 0, 0);
 }
 
 // LDS-DMA the compiler must not see.  hipcc tracks every `buffer_load ... lds` it emits and puts s_waitcnt vmcnt(0) in front of the next
@@ -77,7 +77,7 @@ __device__ __forceinline__ void dma4x(unsigned lds_addr, __amdgpu_buffer_rsrc_t 
     else asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds" :: "s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
 }
 __device__ __forceinline__ void stage_tile_x(const tile_src_t& t, int row0, char* lds, int wave) {
-    const unsigned so = (unsigned)(row0 * t.row_bytes), la = (unsigned)(uintptr_t)lds + (unsigned)(wave * 2) * 1024u;
+    const unsigned so = (unsigned)row0 * t.row_bytes, la = (unsigned)(uintptr_t)lds + (unsigned)(wave * 2) * 1024u;
 #pragma unroll
     for (int i = 0; i < 2; ++i) dma16x<0>(la + i * 1024u, t.rs, t.vo[i], so);
 }
@@ -503,6 +503,26 @@ static int check_strides(int64_t rs, const char* n) {
     if (rs % 8 != 0) { dicow_set_error("attention: %s row stride must be a multiple of 8 elements", n); return 0; }
     return 1;
 }
+// The operands staged through make_tile_src (K and V; in the backward also Q and dO) are addressed with 32-bit byte offsets from the
+// (batch, head) base: the descriptor's num_records = ((L - 1) rs + 64) * 2 is an `unsigned`, and so are the per-lane offset
+// row_in_tile * rs * 2 + chunk (row_in_tile <= 63) and the scalar tile offset row0 * rs * 2 of stage_tile / stage_tile_x / dma16x.
+// Offsets of rows past L are formed too (they must read as zero), the fused backward's second key tile at 64 * rs * 2 included,
+// so at least 65 rows count: the limit is (max(L, 65) - 1) * rs * 2 + 128 < 2^32, which keeps EACH of the two offsets below 2^32.
+// Their SUM is not kept below 2^32: for a padded row of the last tile (L = 100 at the limit: tile offset 64 rows + lane offset 63
+// rows = 127 * rs * 2, about 5.5e9) it passes it.  That such a row reads as zero rests on the hardware's range check of a raw
+// buffer, which compares the lane offset with num_records - scalar offset and does not form a wrapped 32-bit sum; the cases of
+// tests/test_gpu_far_offsets.py at the limit (rows past L surrounded by NaN) hold that on gfx950.  Past the limit the call is
+// refused -- a truncated num_records would make rows read as zero and the call return DICOW_OK with wrong numbers.
+constexpr int64_t ATTN_TILE_SPAN_LIMIT = 1ll << 32;
+static int check_tile_span(int64_t rs, int L, const char* fn, const char* n) {
+    const int64_t rows = L > 65 ? L : 65;
+    if (rs > (ATTN_TILE_SPAN_LIMIT - 129) / (2 * (rows - 1))) {
+        dicow_set_error("%s: %s spans (max(L, 65) - 1) * row stride * 2 + 128 = %lld bytes with L = %d, row stride %lld; the limit is below 2^32 "
+                        "(32-bit tile offsets)", fn, n, (long long)(rows - 1) * (long long)rs * 2 + 128, L, (long long)rs);
+        return 0;
+    }
+    return 1;
+}
 
 // ------------------------------------------------------------------------------------------------ host dispatch, forward
 // Validate, plan, launch.  attn_fwd_plan / attn_bwd_plan are host arithmetic on the arguments alone -- no HIP call, no validation --
@@ -527,6 +547,7 @@ static int attn_fwd_validate(const dicow_attn_fwd_args* a) {
     if (!check_strides(a->q_rs, "q") || !check_strides(a->k_rs, "k") || !check_strides(a->v_rs, "v") ||
         !check_strides(a->o_rs, "o")) return DICOW_ERR_INVALID;
     DICOW_REQUIRE(a->q_bs % 8 == 0 && a->k_bs % 8 == 0 && a->v_bs % 8 == 0 && a->o_bs % 4 == 0, "attn_fwd: batch strides must keep 16-byte alignment");
+    if (!check_tile_span(a->k_rs, a->Lk, "attn_fwd", "k") || !check_tile_span(a->v_rs, a->Lk, "attn_fwd", "v")) return DICOW_ERR_INVALID;
     return DICOW_OK;
 }
 
@@ -1560,6 +1581,8 @@ static int attn_bwd_validate(const dicow_attn_bwd_args* a) {
     for (int i = 0; i < 16; ++i) DICOW_REQUIRE(rs[i] % 4 == 0, "attn_bwd: strides must keep 8-byte alignment");
     DICOW_REQUIRE(a->q_rs % 8 == 0 && a->k_rs % 8 == 0 && a->v_rs % 8 == 0 && a->do_rs % 8 == 0, "attn_bwd: q/k/v/dO row strides %% 8");
     DICOW_REQUIRE(!a->fused_ws || (((uintptr_t)a->fused_ws & 4095) == 0), "attn_bwd: fused_ws must be 4096-byte aligned");
+    if (!check_tile_span(a->k_rs, a->Lk, "attn_bwd", "k") || !check_tile_span(a->v_rs, a->Lk, "attn_bwd", "v") ||
+        !check_tile_span(a->q_rs, a->Lq, "attn_bwd", "q") || !check_tile_span(a->do_rs, a->Lq, "attn_bwd", "d_o")) return DICOW_ERR_INVALID;
     return DICOW_OK;
 }
 
