@@ -971,6 +971,38 @@ int dicow_multi_sumsq_f32(const dicow_mt_tensor* tensors, const dicow_mt_chunk* 
 /* g *= coef[0] in place, coef read from device memory (out + 2 of dicow_multi_sumsq_f32). */
 int dicow_multi_scale_f32(const dicow_mt_tensor* tensors, const dicow_mt_chunk* chunks, int64_t n_chunks, const float* coef, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ tensor statistics (ABI 7, additive)
+ * Per-tensor statistics and histograms over a multi-tensor table (watch.py; the reference's `watch_grads`, src/utils/trainers.py:19-28:
+ * wandb.watch(log='all') logs a 64-bin histogram of every parameter and gradient).  `which` (0..3) picks the column p, g, m or v of the
+ * table; first_chunk[n_tensors + 1] (device, int64) is each tensor's chunk range (chunks are in table order; optim.first_chunks).
+ * Per tensor ONE 64-byte record:
+ *   sum, sumsq        over the FINITE elements, in double: one partial per table chunk, a tensor's partials added in chunk order -- the
+ *                     bits depend on the data and the table only, never on a grid
+ *   min, max, absmax  over the finite elements; none: min = +inf, max = -inf, absmax = 0.  Which signed zero is returned is unspecified
+ *   n_nan, n_posinf, n_neginf, n_zero   exact counts (n_zero: both signs); n_finite = n - n_nan - n_posinf - n_neginf
+ * and, with bins >= 1, hist[t * bins + b] (int64; OVERWRITTEN, not accumulated) over the finite elements:
+ *   min == max : every finite element in bin 0 (the host renders wandb's one-bin form)
+ *   otherwise  : b = min(bins - 1, (int)((x - min) * (float)bins / (max - min))), every operation rounded to fp32, the division the
+ *                correctly rounded one; where max - min overflows fp32 the same formula on x/2, min/2, max/2 (torch.histc is undefined
+ *                there).  The conversion saturates: a quotient of +inf ((x - min) * bins overflowed) is the last bin.
+ * bins = 0 skips the histogram pass (hist may be NULL).  Three launches on `stream`, no host synchronisation, capturable; integer adds
+ * only (no float atomics).  ws: dicow_tensor_stats_ws_bytes() bytes, 16-byte aligned, any contents; one call in flight per workspace.
+ * grid: 0 = default, > 0 forces every pass's grid (tests: the results do not depend on it).  n_tensors = 0 or only empty tensors: valid.
+ * DICOW_ERR_INVALID (dicow_last_error names the limit): bins outside 0..DICOW_STATS_MAX_BINS, which outside 0..3, a short or misaligned
+ * workspace, NULL arguments.  The table lives on the device, so the call cannot see a NULL column pointer of a non-empty tensor: the
+ * host side (watch.tensor_stats) refuses it when it builds the table, and the kernels treat such a tensor as empty instead of reading. */
+#define DICOW_STATS_MAX_BINS 128
+typedef struct {
+    double sum, sumsq;
+    float min, max, absmax;
+    int32_t reserved;       /* 0 */
+    int64_t n_nan, n_posinf, n_neginf, n_zero;
+} dicow_tensor_stats_rec;   /* 64 bytes */
+int64_t dicow_tensor_stats_ws_bytes(int64_t n_tensors, int64_t n_chunks, int bins);
+int dicow_tensor_stats_f32(const dicow_mt_tensor* tensors, const dicow_mt_chunk* chunks, int64_t n_tensors, int64_t n_chunks,
+                           const int64_t* first_chunk, int which, int bins, void* ws, int64_t ws_bytes,
+                           dicow_tensor_stats_rec* out, int64_t* hist, int grid /* 0: default; >0: forced, for tests */, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------------ EXPERIMENTAL (not part of the stable ABI)
  * Declared only under -DDICOW_EXPERIMENTAL_ABI and exported only by a library built with -DDICOW_EXPERIMENTS (build.sh --exp -> libdicow_hip_exp.so).

@@ -147,6 +147,8 @@ class CtcPrefixArgs(C.Structure):
 
 
 MT_MAX_CLASSES = 32
+STATS_MAX_BINS = 128               # DICOW_STATS_MAX_BINS
+STATS_REC_BYTES = 64               # sizeof(dicow_tensor_stats_rec)
 
 
 class MtAdamwClasses(C.Structure):
@@ -232,6 +234,7 @@ _SIGS = {
     "dicow_multi_adamw_f32": [c_vp, c_vp, c_i64, C.POINTER(MtAdamwClasses), c_i, c_vp, c_vp],
     "dicow_multi_sumsq_f32": [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_f, c_vp],
     "dicow_multi_scale_f32": [c_vp, c_vp, c_i64, c_vp, c_vp],
+    "dicow_tensor_stats_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i, c_i, c_vp, c_i64, c_vp, c_vp, c_i, c_vp],
 }
 
 
@@ -300,6 +303,7 @@ _SIGS64 = {   # functions returning int64_t (workspace sizes)
     "dicow_scb_gate_bwd_ws_bytes": [],
     "dicow_ctc_ws_bytes": [c_i, c_i, c_i],
     "dicow_multi_sumsq_ws_bytes": [c_i64],
+    "dicow_tensor_stats_ws_bytes": [c_i64, c_i64, c_i],
     "dicow_lora_wgrad_ws_bytes": [c_i, c_i, c_i, c_i, c_i],
     "dicow_noise_mix_ws_bytes": [c_i, c_i],
     "dicow_diar_table_ws_bytes": [c_i],

@@ -662,3 +662,24 @@ def multi_sumsq(tensors_ptr, chunks_ptr, n_chunks, ws, out, max_norm):
 def multi_scale(tensors_ptr, chunks_ptr, n_chunks, coef):
     """Every g *= coef[0] (a device float) in place."""
     L.call("dicow_multi_scale_f32", tensors_ptr, chunks_ptr, n_chunks, coef.data_ptr(), L.stream())
+
+
+# ---- per-tensor statistics and histograms over the same table (dicow_tensor_stats_*; watch.py builds the table and reads the results)
+def tensor_stats_ws_bytes(n_tensors, n_chunks, bins) -> int:
+    return int(L.lib().dicow_tensor_stats_ws_bytes(n_tensors, n_chunks, bins))
+
+
+def tensor_stats(tensors_ptr, chunks_ptr, n_tensors, n_chunks, first_chunk_ptr, which, bins, ws, out, hist, grid=0):
+    """Column `which` (0..3: p, g, m, v) of every tensor of a device table -> out: uint8 device tensor of n_tensors 64-byte records
+    (dicow_tensor_stats_rec), hist: int64 [n_tensors, bins] (None with bins = 0), overwritten.  ws: uint8 device tensor of at least
+    tensor_stats_ws_bytes() bytes (any contents; None when that is 0), one call in flight at a time.  grid > 0 forces the grids."""
+    if out is not None:
+        _req(out, torch.uint8, "tensor_stats: out")
+        if out.numel() < n_tensors * L.STATS_REC_BYTES:
+            raise L.DicowError(f"tensor_stats: out holds {out.numel()} bytes, {n_tensors * L.STATS_REC_BYTES} needed")
+    if hist is not None:
+        _req(hist, torch.int64, "tensor_stats: hist")
+        if hist.numel() < n_tensors * bins:
+            raise L.DicowError(f"tensor_stats: hist holds {hist.numel()} counts, {n_tensors * bins} needed")
+    L.call("dicow_tensor_stats_f32", tensors_ptr, chunks_ptr, n_tensors, n_chunks, first_chunk_ptr, int(which), int(bins),
+           None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), _p(out), _p(hist), int(grid), L.stream())

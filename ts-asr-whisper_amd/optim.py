@@ -68,6 +68,15 @@ def build_table(ptrs, numels, cls=None):
     return tensors, chunks
 
 
+def first_chunks(numels):
+    """int64 [T + 1]: tensor i owns the chunks [first[i], first[i + 1]) of build_table's chunk list (table order; an empty tensor owns
+    none).  What the per-tensor passes of csrc/tensor_stats.hip walk."""
+    nch = (np.asarray(numels, dtype=np.int64) + CHUNK - 1) // CHUNK
+    first = np.zeros(nch.shape[0] + 1, np.int64)
+    np.cumsum(nch, out=first[1:])
+    return first
+
+
 class _DeviceTable:
     """One device copy of a table, refreshed through a pinned staging buffer.  The event of the last copy guards the staging buffer:
     it is rewritten only after the copy out of it has run (at a rebuild, never per step).  Kernels read the device copy in stream

@@ -557,8 +557,13 @@ class TrainStep:
     def __init__(self, model, lr=2e-6, fddt_lr_multiplier=100.0, weight_decay=0.0, max_grad_norm=1.0, warmup_steps=0,
                  max_steps=0, frozen_keywords=("decoder",), preheat_prefixes=None,
                  process_group=None, augmenter=None, use_fddt_only_n_steps=0, graph=False, use_fddt_only_n_epochs=0,
-                 steps_per_epoch=None, replica_sync="broadcast", split_streams=False, front_end=None):
+                 steps_per_epoch=None, replica_sync="broadcast", split_streams=False, front_end=None, watch=None):
         self.model = model
+        # watch: a watch.GradWatch (the reference's `watch_grads`).  After every log_freq-th step, outside any captured graph: the flat
+        # store's gradients still hold that step's exchanged values (the fused AdamW applies the clip coefficient on the fly and the
+        # next zero_grad has not run), so a record is "gradients of step k as the optimizer saw them before clipping, parameters
+        # after update k".  None: not a launch differs.
+        self.watch = watch
         # split_streams=True: a batch of even size B >= 2 runs as two half batches on two HIP streams (same loss and gradients: the
         # halves' losses are weighted by their label counts, their gradients add in a fixed order -- SplitSync).  The HBM-bound row
         # kernels, the attention tails and the partial last rounds of one half fill under the other half's matrix kernels
@@ -810,8 +815,12 @@ class TrainStep:
         With graph=True a single batch replays the captured step (`eager=True` forces the launch-by-launch path)."""
         micro = list(batch) if isinstance(batch, (list, tuple)) else [batch]
         if self.graph and not eager and len(micro) == 1:
-            return self._graph_step(micro[0])
-        return self._eager_step(micro)
+            loss = self._graph_step(micro[0])
+        else:
+            loss = self._eager_step(micro)
+        if self.watch is not None and self.watch.due(self.global_step):
+            self.watch.collect(self.global_step)
+        return loss
 
     def _eager_step(self, micro):
         self.begin_step()
