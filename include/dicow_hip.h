@@ -770,6 +770,51 @@ int dicow_ngram_repeats(const int32_t* ids, const int32_t* fold, int64_t n_words
                         int min_words, int unigram_min_repeat, int repeat_threshold, int32_t* keep, int32_t* reason, int plan, void* ws,
                         int64_t ws_bytes, void* stream);
 
+/* Bootstrap and randomisation sums of integer count columns (ABI 7, additive): the one primitive behind a bootstrap confidence interval
+ * of an error rate, the paired bootstrap of the difference of two systems and the paired approximate-randomisation test -- sums of the
+ * columns of a table of counts over R random multisets of its rows, all replicates in one launch.
+ * table: device int64 [n][C], row-major, leading dimension ld >= C in elements: one row per unit (session, utterance), one column per
+ * count.  1 <= n <= DICOW_BOOT_MAX_N, 1 <= C <= DICOW_BOOT_MAX_C.  strata: a HOST array of S + 1 = n_strata + 1 ascending offsets with
+ * offs[0] = 0 and offs[S] = n, every stratum non-empty (S = 1: no stratification); strata_dev: the same S + 1 int64 offsets in device
+ * memory (may be NULL when S == 1 or mode is DICOW_BOOT_SWAP: then nothing reads them).  out: device int64 [R][C], dense.
+ * THE DEFINITION.  The random word for replicate r and slot p is
+ *   w(r, p, t) = Philox4x32-10(counter = (p >> 2, r & 0xffffffff, r >> 32, t), key = (seed & 0xffffffff, seed >> 32))[p & 3]
+ * where r is the absolute replicate number first_replicate + row (64-bit, wrapping) and Philox4x32-10 is the Random123 function with
+ * multipliers 0xD2511F53 / 0xCD9E8D57 and key increments 0x9E3779B9 / 0xBB67AE85.
+ *   Resample mode (DICOW_BOOT_RESAMPLE, t = 0):  out[row, c] = sum over p in [0, n) of table[lo_s + ((w * n_s) >> 32), c]
+ *     where s is the stratum that holds slot p, lo_s is its first unit and n_s is its size: each replicate draws exactly n_s units, with
+ *     replacement, from each stratum.  The multiply-high mapping has a bias of at most n_s / 2^32: a unit's probability differs from
+ *     1 / n_s by less than 2^-32.
+ *   Swap mode (DICOW_BOOT_SWAP, t = 1, C even, h = C / 2):  b = w & 1, and out[row, c] = sum over p of table[p, (c + h*b) mod C].
+ *     Columns [0, h) belong to system A and [h, C) to system B; a set bit exchanges the two systems' counts of unit p.  Strata are ignored.
+ * Plain int64 adds, no atomics, one writer per output element; one replicate never spans more than one workgroup, so there is no
+ * cross-workgroup reduction and no workspace; one launch, no host read: the call can be captured into a graph.  Because the sums are
+ * integers and the words depend only on (seed, r, p, t), the output is identical under every plan, grid and chunking of the R replicates
+ * into calls.  PRECONDITION (not checked here; the Python wrapper checks it with one reduction): n * max|table| < 2^62.  Negative entries
+ * are allowed.
+ * plan: 0 = the library's choice for the call (dicow_bootstrap_plan names it), or 1 .. DICOW_BOOT_PLANS (tests, measurements):
+ *   1 DICOW_BOOT_LANE_LDS  a lane owns a whole replicate, the table staged in LDS (256 replicates a workgroup),
+ *   2 DICOW_BOOT_WAVE_LDS  a wave owns a replicate: each lane evaluates one Philox block for four consecutive slots a step and keeps C
+ *                          sums in registers, a wave reduction at the end; the table staged in LDS (64 replicates a workgroup),
+ *   3 DICOW_BOOT_WAVE_L2   the same with the table read through L2 (4 replicates a workgroup).
+ * Plans 1 and 2 need n * C * 8 <= DICOW_BOOT_LDS_BYTES and are refused otherwise.
+ * Checked on the host before anything is launched (-1, dicow_last_error() names it): n, C, ld, R in [0, DICOW_BOOT_MAX_R], the mode (and
+ * C even in swap mode), the plan and whether the table fits it, the strata (first 0, last n, ascending, none empty), pointers and their
+ * 8-byte alignment.  R == 0 succeeds and writes nothing. */
+#define DICOW_BOOT_MAX_N 16777216
+#define DICOW_BOOT_MAX_C 32
+#define DICOW_BOOT_MAX_R 2147483647LL
+#define DICOW_BOOT_LDS_BYTES 65536
+#define DICOW_BOOT_PLANS 3
+#define DICOW_BOOT_LANE_LDS 1
+#define DICOW_BOOT_WAVE_LDS 2
+#define DICOW_BOOT_WAVE_L2 3
+#define DICOW_BOOT_RESAMPLE 0
+#define DICOW_BOOT_SWAP 1
+int dicow_bootstrap_plan(int n, int C);      /* the plan that plan = 0 stands for; -1 for n or C out of range */
+int dicow_bootstrap_sums(const int64_t* table, int64_t ld, int n, int C, const int64_t* strata, const int64_t* strata_dev, int n_strata,
+                         int64_t R, uint64_t first_replicate, uint64_t seed, int mode, int plan, int64_t* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ batch augmentation
  * The collator's training-time augmentations (reference src/data/collators.py:189-214), applied to the batch where it
  * already lives (HBM).  The random decisions are drawn on the host from the torch CPU generator in the reference's

@@ -31,6 +31,8 @@ from .diar_scoring import (unscored_intervals, diar_score_counts, split_counts, 
                            score_diarizations)
 from .hyp_cleanup import (repeating_ngram_cuts, truncate_repeating_ngrams, truncate_at_repeating_ngram,  # noqa: F401
                           session_hypotheses)
+from .significance import (bootstrap_sums, percentile_interval, ratio_interval, compare_ratios, session_metric_intervals,  # noqa: F401
+                           compare_session_metrics, wer_interval, compare_wer)
 from .optim import DiCoWAdamW, clip_grad_norm_, dicow_optimizer  # noqa: F401
 from .watch import tensor_stats, TensorStats, GradWatch, WatchCallback, as_wandb, jsonl_sink  # noqa: F401
 
@@ -47,4 +49,6 @@ __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalG
            "format_alignment", "session_alignment", "error_breakdown", "save_alignment_report", "unscored_intervals", "diar_score_counts", "split_counts", "mapping_from_counts",
            "error_from_counts", "jaccard_from_counts", "aggregate_diarization_scores", "diarization_error", "jaccard_error", "optimal_mapping",
            "score_diarizations", "CtcAlignment", "ctc_forced_align", "token_timestamps", "word_timestamps", "align_segments",
-           "words_as_segments", "tensor_stats", "TensorStats", "GradWatch", "WatchCallback", "as_wandb", "jsonl_sink", "repeating_ngram_cuts", "truncate_repeating_ngrams", "truncate_at_repeating_ngram", "session_hypotheses"]
+           "words_as_segments", "tensor_stats", "TensorStats", "GradWatch", "WatchCallback", "as_wandb", "jsonl_sink", "repeating_ngram_cuts", "truncate_repeating_ngrams", "truncate_at_repeating_ngram", "session_hypotheses",
+           "bootstrap_sums", "percentile_interval", "ratio_interval", "compare_ratios", "session_metric_intervals", "compare_session_metrics",
+           "wer_interval", "compare_wer"]

@@ -7,6 +7,7 @@ LIB_PATH = os.environ.get("DICOW_HIP_LIB") or os.path.join(_HERE, "libdicow_hip.
 _lib = None
 
 c_vp, c_i, c_i64, c_f, c_d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
+c_u64 = C.c_uint64
 
 
 class FddtLnFwdArgs(C.Structure):
@@ -94,6 +95,11 @@ DIAR_SCORE_MAX_E, DIAR_SCORE_MAX_TICK, DIAR_SCORE_MAX_WS_BYTES = 1 << 24, 1 << 4
 # DICOW_NGRAM_*: dicow_ngram_repeats's longest n-gram, longest segment, number of plans, workspace limit and table bytes per segment / item
 NGRAM_MAX_N, NGRAM_MAX_WORDS, NGRAM_PLANS, NGRAM_MAX_WS_BYTES, NGRAM_SEG_BYTES, NGRAM_ITEM_BYTES = 16, 65535, 4, 1 << 30, 24, 8
 NGRAM_PLAN_TILES = {1: (64, 256), 2: (64, 1024), 3: (256, 256), 4: (256, 1024)}   # plan -> (R rows a workgroup, C words a chunk)
+
+# DICOW_BOOT_*: dicow_bootstrap_sums's limits, the bytes of LDS its staged plans may fill, its plans and modes
+BOOT_MAX_N, BOOT_MAX_C, BOOT_MAX_R, BOOT_LDS_BYTES, BOOT_PLANS = 1 << 24, 32, (1 << 31) - 1, 65536, 3
+BOOT_LANE_LDS, BOOT_WAVE_LDS, BOOT_WAVE_L2 = 1, 2, 3
+BOOT_RESAMPLE, BOOT_SWAP = 0, 1
 
 LORA_MAX_R, LORA_MAX_SEG = 192, 24
 LORA_BLOCK, LORA_OUT_F32, LORA_GELU, LORA_MUL_AUX = 1, 2, 4, 8
@@ -225,6 +231,8 @@ _SIGS = {
     "dicow_orc_distance": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "dicow_diar_score": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_vp, c_vp, c_i64, c_vp],
     "dicow_ngram_repeats": [c_vp, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp, c_i, c_vp, c_i64, c_vp],
+    "dicow_bootstrap_plan": [c_i, c_i],
+    "dicow_bootstrap_sums": [c_vp, c_i64, c_i, c_i, c_vp, c_vp, c_i, c_i64, c_u64, c_u64, c_i, c_i, c_vp, c_vp],
     "dicow_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
     "dicow_fabric_emulate": [c_vp, c_i64, c_d, c_i, c_i, c_vp],
     "dicow_adamw_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_i, c_vp, c_f, c_vp],
