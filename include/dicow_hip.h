@@ -480,14 +480,26 @@ int64_t dicow_noise_mix_ws_bytes(int n_plan, int max_len);
 int dicow_noise_mix(const float* wave, int64_t ld_wave, float* out, int64_t ld_out, const float* bank, const int64_t* clip_start,
                     const int* clip_len, const int* plan_i, const float* plan_snr, int n_plan, void* ws, int64_t ws_bytes, void* stream);
 
+/* HOST TABLES.  The table-driven entry points below -- the diarization front end, dicow_resample, dicow_edit_distance,
+ * dicow_edit_alignment, dicow_orc_distance, dicow_diar_score, dicow_ngram_repeats, dicow_ctc_forced_align -- take their tables (what a
+ * comment calls a HOST pointer) from host memory, and one rule holds for all of them:
+ *   - a table is checked in full before anything is launched; a refusal returns -1 with dicow_last_error() set and has launched nothing;
+ *   - what the kernels read of it (the table itself, or descriptors built from it) is copied into the head of the caller's workspace on
+ *     the stream, ahead of the launches;
+ *   - the caller keeps the tables valid and unchanged until the call returns.  The library ASSUMES that a copy from pageable host memory
+ *     has read its source by then: an assumption about the HIP runtime that has not been measured here.  A caller who passes pinned
+ *     memory keeps it until the stream has passed the copy;
+ *   - under stream capture the library keeps a copy of its own of every table for the life of the process, and the graph's copy nodes
+ *     read that: a replay never reads caller memory or the image of a later call.  This is what "capturable" means below. */
+
 /* Diarization front end (ABI 7, additive): a diarization -- (speaker, start, end) segments -- to the STNO masks and the self-enrollment
  * windows of SE-DiCoW, without a per-sample mask anywhere (reference src/data/local_datasets.py: get_stno_mask :162-182,
  * _create_stno_masks :184-194, sample_enrollment_window / downsample_mean / select_random_internal_enrollment :216-292).
  * The diarization arrives as a table the host builds in one sweep over the interval endpoints (ts-asr-whisper_amd/diar_front_end.py):
  *   bounds int64 [E + 1], strictly increasing, 0 <= bounds[0], bounds[E] <= n_samples;
  *   active uint64 [E]: bit s set when speaker s (0 <= s < S <= 64) is active on the samples [bounds[e], bounds[e + 1]).
- * `bounds`, `active` and `targets` are HOST pointers: every entry point checks them before anything is launched (and returns -1 with
- * dicow_last_error() set when they are bad) and then copies them into its workspace with the stream; everything else is device memory.
+ * `bounds`, `active` and `targets` are HOST pointers (HOST TABLES above; all three entry points are capturable); everything else is
+ * device memory.
  * Frames are DICOW_DIAR_FRAME samples (one encoder frame), bins DICOW_DIAR_BIN samples (0.1 s = 5 frames), windows DICOW_DIAR_WINDOW bins
  * (30 s); T_total = ceil(n_samples / 480000) * 1500.  All three: integer arithmetic or correctly rounded fp32 in a fixed order, one writer
  * per output element, no atomics, nothing allocated, bit-identical from run to run and whatever else is asked for in the same call.
@@ -559,7 +571,7 @@ int dicow_enrollment_mix(float* out, int64_t ld_out, int B, int n, const float* 
  *   sample / 32768 per channel, the channel sum (both exact), one correctly rounded division by C -- the bits of torch.mean(pcm / 32768, 0).
  * Nothing outside a segment is read (in_frames, out_samples: the sizes of the two buffers), nothing outside its ceil(n in_len / o)
  * output samples is written, and every output sample has one writer and one order of summation: its bits do not depend on
- * frames_per_tile, the grid, or the other segments of the call.  No atomics; one launch behind one copy, capturable.
+ * frames_per_tile, the grid, or the other segments of the call.  No atomics; one launch behind one copy, capturable (HOST TABLES above).
  * Checked on the host before anything is launched (-1, dicow_last_error()): 1 <= o, n <= DICOW_RESAMPLE_MAX_RATIO; 1 <= S <= 2 width + o;
  * first[p] in [0, 2 width + o); every segment inside the stated buffer sizes, lengths >= 0; the output ranges pairwise disjoint; the
  * pointers aligned (in, out: their element size; taps_t: 16 bytes; ws: 8 bytes); and the LDS budget: a workgroup keeps the input span of
@@ -567,7 +579,7 @@ int dicow_enrollment_mix(float* out, int64_t ld_out, int B, int n, const float* 
  * 4 S n <= DICOW_RESAMPLE_LDS_BYTES / 2, the bank (it is read from memory otherwise) in DICOW_RESAMPLE_LDS_BYTES of LDS.  frames_per_tile = 0 lets
  * the library choose (about 4096 output samples per tile, or what fits); a ratio whose single frame does not fit is refused, and so is a
  * frames_per_tile that does not.  in and out must not overlap (unchecked: device memory).  ws: dicow_resample_ws_bytes(n_segs, n) bytes;
- * the table and first[] are copied there with the stream.  n_segs == 0, or segments that are all empty, launch nothing. */
+ * the table and first[] go there.  n_segs == 0, or segments that are all empty, launch nothing. */
 #define DICOW_RESAMPLE_LDS_BYTES 49152
 #define DICOW_RESAMPLE_MAX_RATIO 1048576
 #define DICOW_RESAMPLE_MAX_CHANNELS 512
@@ -595,9 +607,8 @@ int dicow_resample(const void* in, int in_int16, int C, int channel, int64_t in_
  * packed E * 2^15 - H in int32 when ref_len + hyp_len <= 65535 - DICOW_EDIT_LANES * DICOW_EDIT_K for every pair, E * 2^32 - H in int64 otherwise.
  * Checked on the host before anything is launched (-1, dicow_last_error()): lengths in [0, DICOW_EDIT_MAX_LEN], spans inside n_ref / n_hyp,
  * intervals for both sides or neither, lanes / along, pointers and their alignment, ws_bytes.  ws: dicow_edit_distance_ws_bytes(pairs,
- * n_pairs) bytes, 8-byte aligned: the table (copied there with the stream) and the boundary columns; -1 for a table the call would refuse
- * for its lengths.  One launch behind one copy, no atomics, capturable (a captured call's table image stays allocated: the copy node reads
- * it at every replay).  n_pairs == 0 launches nothing. */
+ * n_pairs) bytes, 8-byte aligned: the table and the boundary columns; -1 for a table the call would refuse for its lengths.  One launch
+ * behind one copy, no atomics, capturable (HOST TABLES above).  n_pairs == 0 launches nothing. */
 #define DICOW_EDIT_MAX_LEN 65535
 #define DICOW_EDIT_K 8
 #define DICOW_EDIT_LANES 512
@@ -683,8 +694,8 @@ int dicow_orc_distance(const int32_t* ref_ids, int64_t n_ref, const int32_t* hyp
  * arithmetic on ticks (samples), without a per-sample mask.  A problem has two tables of the diarization front end (bounds int64 [E + 1]
  * strictly increasing, active uint64 [E], bit s = speaker s < S <= 64 talks on [bounds[e], bounds[e + 1]); E == 0 is an empty table whose
  * one bound is not read), a sorted list of disjoint half-open UNSCORED intervals [u0, u1) (they may touch), and a skip_overlap flag.
- * All tables are HOST memory (checked in full, then copied into the workspace with the stream from where they are: they stay valid until
- * the stream has made the copies, which for pageable memory is when the call returns), concatenated: bounds int64 [n_bounds], active uint64 [n_active], unscored int64 [n_unscored][2], and
+ * All tables are HOST memory (HOST TABLES above; the three arrays are copied from where they are, without a staging copy on the host),
+ * concatenated: bounds int64 [n_bounds], active uint64 [n_active], unscored int64 [n_unscored][2], and
  * problems int64 [n_problems][DICOW_DIAR_SCORE_ROW] =
  *   (ref_bounds_first, ref_active_first, Er, Sr, hyp_bounds_first, hyp_active_first, Eh, Sh, unscored_first, n_unscored, skip_overlap, 0):
  *   the reference's bounds are bounds[ref_bounds_first .. + Er], its bitmasks active[ref_active_first .. + Er - 1], and so on.
@@ -752,8 +763,7 @@ int dicow_diar_score(const int64_t* bounds, int64_t n_bounds, const uint64_t* ac
  * every n at once the j whose match is at least n words long; it min-reduces one packed key (keep, n, count) per item.  A second launch of
  * one wave per segment folds the items, finds i0 from the run boundaries and writes keep and reason.  plan: 0 = the library's choice for the
  * call, or 1 .. DICOW_NGRAM_PLANS for (R, C) = (64, 256), (64, 1024), (256, 256), (256, 1024) (tests, measurements); a segment's result
- * depends neither on the plan nor on the other segments.  One copy (the tables, into ws, on the stream) and two launches, no host read:
- * the call can be captured into a graph.
+ * depends neither on the plan nor on the other segments.  One copy and two launches, no host read: capturable (HOST TABLES above).
  * ws: dicow_ngram_repeats_ws_bytes(table, n, plan) bytes, 16-byte aligned, at most DICOW_NGRAM_MAX_WS_BYTES: DICOW_NGRAM_SEG_BYTES a
  * segment and DICOW_NGRAM_ITEM_BYTES a possible work item (ceil((W - 1) / R) a segment), rounded up to 16, and 8 bytes a possible item.
  * Checked on the host before anything is launched (-1, dicow_last_error() names the limit): W in [0, DICOW_NGRAM_MAX_WORDS]; plan; the
@@ -931,8 +941,8 @@ int dicow_ctc_greedy_decode(const void* logits, int in_bf16, int64_t batch_strid
  * Launches: a gather of the compact emission matrix E (per problem F rows of W = roundup8(L) + 4 floats: the targets' x, -inf up to a
  * multiple of 8, the blank's x, three zeros), then one wave per problem: the frame recursion with 16 (wide plan) or 2 (narrow plan, L <=
  * 63) states per lane in registers, 2-bit back-pointers stored per frame, and the walk back through blocks of 64 frames of them staged in
- * LDS.  plan: 0 = narrow for every problem with L <= 63, wide otherwise; 1 / 2 force narrow / wide (tests, measurements).  One copy (the
- * tables, into ws, on the stream) and two launches; no host read: the call can be captured into a graph.
+ * LDS.  plan: 0 = narrow for every problem with L <= 63, wide otherwise; 1 / 2 force narrow / wide (tests, measurements).  One copy
+ * and two launches; no host read: capturable (HOST TABLES above).
  * ws: dicow_ctc_align_ws_bytes(table, n) bytes, 16-byte aligned, at most DICOW_CTC_ALIGN_MAX_WS_BYTES: DICOW_CTC_ALIGN_PROB_BYTES a problem
  * plus 4 bytes a target, rounded up to 16; then per problem 4 F W bytes of E and F * bp_row rounded up to 16 of back-pointers, bp_row =
  * max(4 * ceil((2 L + 1) / 16), roundup4(L + 1) if L <= 63).

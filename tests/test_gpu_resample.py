@@ -172,6 +172,53 @@ def test_guard_bands(W, orig, new, kind, C):
         assert torch.equal(dev.cpu().view(torch.int16), host.view(torch.int16))          # and the input is untouched
 
 
+@pytest.mark.parametrize("orig,new", [(8000, 16000), (44100, 16000)])
+def test_a_captured_call_replays_on_its_own_table(W, orig, new):
+    """A captured resample_segments keeps the segment table it was captured with: another call on the same thread between capture and
+    replay does not change what the replay computes.  Both tables have three rows inside the same src and out (table B: two other
+    segments and an empty row), so that a replay which did read the later call's image would still read rows that exist and stay
+    inside both buffers: wrong samples, never a wrong address."""
+    from ts_asr_whisper_amd import ops
+    plan = W.resample_plan(orig, new, "cuda")
+    n_in = 4000
+    src = R.wave(orig, new, n_in, tag="capture").cuda()
+    seg_a = [(0, 1500, 3), (1500, 1000, 3 + plan.out_len(1500) + 2), (2600, 1400, 3 + plan.out_len(1500) + 2 + plan.out_len(1000) + 5)]
+    seg_b = [(100, 1700, 40), (2000, 1900, 40 + plan.out_len(1700) + 1), (0, 0, 0)]
+    total = max(s[2] + plan.out_len(s[1]) for s in seg_a + seg_b) + 61
+    for segs in (seg_a, seg_b):
+        assert all(0 <= s[0] and s[0] + s[1] <= n_in and 0 <= s[2] and s[2] + plan.out_len(s[1]) <= total for s in segs)
+    canary = _sentinel(total, torch.float32)
+    out = canary.cuda()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        W.resample_segments(src, plan, seg_a, out)                          # (code objects load outside the capture)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    want = out.cpu()
+    inside = torch.zeros(total, dtype=torch.bool)
+    for in_start, in_len, out_start in seg_a:
+        seg = want[out_start: out_start + plan.out_len(in_len)]
+        assert torch.equal(bits(seg), bits(W.resample(src[in_start: in_start + in_len].contiguous(), orig, new)))
+        inside[out_start: out_start + plan.out_len(in_len)] = True
+    assert torch.equal(want.view(torch.int32)[~inside], canary.view(torch.int32)[~inside])
+    out.copy_(canary)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        W.resample_segments(src, plan, seg_a, out)
+        ws = ops.workspace(0, src.device)                                   # the capturing stream's workspace: the call's table lies at its head
+    W.resample_segments(src, plan, seg_b, out)                              # another table, eagerly, before the first replay
+    torch.cuda.synchronize()
+    assert not torch.equal(bits(out), bits(want))
+    for clear_ws in (False, True):
+        out.copy_(canary)
+        if clear_ws:
+            ws[:pkg._lib.lib().dicow_resample_ws_bytes(len(seg_a), plan.n)].zero_()   # the replay uploads the table again
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(bits(out), bits(want)), clear_ws
+
+
 def test_wrapper_refusals_on_the_gpu(W):
     L = pkg._lib
     x = torch.zeros(100, device="cuda")

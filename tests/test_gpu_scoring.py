@@ -236,6 +236,16 @@ def test_side_stream_and_graph_replay():
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         launch(rp, hp, table, go.view, gw.view, nbytes)                  # one linear launch behind its table copy
+    # another eager call on this thread between capture and replay: the replay must not see its table.  As many pairs over the same id
+    # buffers, none longer than the captured ones, so that even a stale image would stay inside `out` and `ws`
+    other = [(3, 0), (0, 3), (2, 2), (0, 0)]
+    table_b = np.array([(rp.starts[i], rp.lens[i], hp.starts[j], hp.lens[j]) for i, j in other], np.int64)
+    gob, gwb, nbytes_b = buffers(table_b)
+    assert nbytes_b <= nbytes
+    launch(rp, hp, table_b, gob.view, gwb.view, nbytes_b)
+    torch.cuda.synchronize()
+    exp_b = expect(refs, hyps, other)
+    assert np.array_equal(gob.view.cpu().numpy(), exp_b) and not np.array_equal(exp_b, exp)
     graph.replay()
     torch.cuda.synchronize()
     assert np.array_equal(go.view.cpu().numpy(), exp)

@@ -106,6 +106,35 @@ def test_workspace_size_follows_the_stated_formula():
     assert _size(lib, pairs, WIDE, 0) == sum(_size(lib, [p], WIDE, 0) for p in pairs)
 
 
+# Pair lists that cross each boundary of the plan, and what dicow_edit_alignment_ws_bytes returned for them -- (lanes = 0, along = 1),
+# (0, 2), (0, 0), (NARROW, 0), (WIDE, 0) -- before dicow_edit_distance and dicow_edit_alignment shared one plan.  The same lists pin
+# dicow_edit_distance_ws_bytes in tests/test_host_scoring.py.
+PLAN_BOUNDARIES = {
+    "shorter side at NARROW * K (narrow)": ([(0, NARROW * K, 0, NARROW * K + 50), (5, 7, 3, 9)], (89128, 89992, 89136, 89136, 91784)),
+    "shorter side one past it (wide)": ([(0, NARROW * K + 1, 0, NARROW * K + 60), (5, 7, 3, 9)], (91968, 93392, 93392, 91344, 93392)),
+    "ref_len + hyp_len at the int32 key's limit": ([(0, 30000, 0, 31439), (0, 3, 1, 4)], (240013272, 240204736, 240204736, 236766168, 240204736)),
+    "one past it (int64 key)": ([(0, 30000, 0, 31440), (0, 3, 1, 4)], (240020792, 240204752, 240204752, 236773688, 240204752)),
+    "empty sides": ([(0, 0, 0, 9), (0, 300, 0, 0), (0, 0, 0, 0), (2, 40, 1, 33)], (600, 664, 600, 600, 600)),
+}
+
+
+def test_workspace_size_at_the_plan_boundaries():
+    """The header's formula with along = 1 and 2 on lists that cross narrow -> wide and the 32- -> 64-bit key or have an empty side
+    (test_workspace_size_follows_the_stated_formula covers one and two panels and the library's choice of `along` on single pairs), and
+    equality with the values recorded before the two plans were merged."""
+    lib = _lib.lib()
+    T = _lib.ALIGN_TABLE_BYTES
+    assert 30000 + 31439 == 65535 - WIDE * K
+    for name, (pairs, recorded) in PLAN_BOUNDARIES.items():
+        lanes = WIDE if any(min(p[1], p[3]) > NARROW * K for p in pairs) else NARROW
+        bnd = sum(16 * max(p[1], p[3]) for p in pairs if max(p[1], p[3]) > NARROW * K)
+        for along in (1, 2):
+            rec = sum(_records(p[1], p[3], lanes) if along == 1 else _records(p[3], p[1], lanes) for p in pairs)
+            assert _size(lib, pairs, 0, along) == len(pairs) * T + bnd + rec, (name, along)
+        got = (_size(lib, pairs, 0, 1), _size(lib, pairs, 0, 2), _size(lib, pairs, 0, 0), _size(lib, pairs, NARROW, 0), _size(lib, pairs, WIDE, 0))
+        assert got == recorded, name
+
+
 def test_entry_points_refuse_bad_arguments_before_any_launch():
     lib = _lib.lib()
     for bad, word in (((None, -1, 0, 0), b"negative n_pairs"), ((None, 2, 0, 0), b"null pair table")):

@@ -99,6 +99,23 @@ def test_entry_points_refuse_bad_arguments_before_any_launch():
     assert _call(lib, [], ref=None, hyp=None, out=None, ws=None, wsb=0) == 0
 
 
+def test_workspace_size_at_the_plan_boundaries():
+    """dicow_edit_distance_ws_bytes on pair lists that cross each boundary of the plan it shares with dicow_edit_alignment: the header's
+    formula (40 bytes a pair, 16 bytes a symbol of the longer side when that exceeds DICOW_EDIT_LANES_NARROW * DICOW_EDIT_K), and the
+    values the library returned before the two plans were merged.  (The longer side at the narrow panel and one past it, and a pair of
+    two empty sides, are in test_entry_points_refuse_bad_arguments_before_any_launch.)"""
+    lib = _lib.lib()
+    K, narrow, wide = _lib.EDIT_K, _lib.EDIT_LANES_NARROW, _lib.EDIT_LANES
+    assert 30000 + 31439 == 65535 - wide * K
+    for pairs, recorded in (([(0, narrow * K, 0, narrow * K + 50), (5, 7, 3, 9)], 9072),           # the shorter side at the narrow panel
+                            ([(0, narrow * K + 1, 0, narrow * K + 60), (5, 7, 3, 9)], 9232),       # one past it: the wide workgroup
+                            ([(0, 30000, 0, 31439), (0, 3, 1, 4)], 503104),                        # the int32 key's limit
+                            ([(0, 30000, 0, 31440), (0, 3, 1, 4)], 503120),                        # one past it: the int64 key
+                            ([(0, 0, 0, 9), (0, 300, 0, 0), (0, 0, 0, 0), (2, 40, 1, 33)], 160)):  # empty sides
+        got = lib.dicow_edit_distance_ws_bytes(_table(pairs).ctypes.data, len(pairs))
+        assert got == 40 * len(pairs) + sum(16 * max(p[1], p[3]) for p in pairs if max(p[1], p[3]) > narrow * K) == recorded, pairs
+
+
 def test_wrappers_refuse_cpu_tensors_and_bad_shapes():
     ids = torch.zeros(4, dtype=torch.int32)
     with pytest.raises(_lib.DicowError, match="GPU"):

@@ -18,7 +18,7 @@
 //   plan 3 WAVE_L2    the same, the rows read from global memory: a table past DICOW_BOOT_LDS_BYTES stays in L2 (640 KB at 20 000 x 4).
 // Rows are read 16 bytes a load where C and the row pitch are even (in swap mode under plan 3 with 2 or 4 columns); the staging copies 16
 // bytes a lane where the table is dense.  Which plan the library picks where: dicow_bootstrap_plan, measured in profiles/bootstrap.txt.
-#include "common.h"
+#include "host_table.h"
 #include <algorithm>
 
 #define BS_THREADS 256
@@ -262,7 +262,7 @@ extern "C" int dicow_bootstrap_sums(const int64_t* table, int64_t ld, int n, int
     if (R == 0) return DICOW_OK;
     const bool reads_strata = n_strata > 1 && mode == DICOW_BOOT_RESAMPLE;
     DICOW_REQUIRE(table && out && (strata_dev || !reads_strata), "bootstrap_sums: null pointer");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(table) % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0 && reinterpret_cast<uintptr_t>(strata_dev) % 8 == 0,
+    DICOW_REQUIRE(dicow_aligned(8, table, out, strata_dev),
                   "bootstrap_sums: table / out / strata_dev not 8-byte aligned");
     bs_args a;
     a.table = table; a.offs = strata_dev; a.out = out;
@@ -270,7 +270,7 @@ extern "C" int dicow_bootstrap_sums(const int64_t* table, int64_t ld, int n, int
     a.r0 = first_replicate;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
     a.n = n; a.C = C; a.S = reads_strata ? n_strata : 1;
-    const bool aligned16 = reinterpret_cast<uintptr_t>(table) % 16 == 0;
+    const bool aligned16 = dicow_aligned(16, table);
     a.vec_stage = ld == C && aligned16 && ((int64_t)n * C) % 2 == 0;
     int CT = 1;
     while (CT < C) CT *= 2;

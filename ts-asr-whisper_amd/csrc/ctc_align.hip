@@ -27,7 +27,7 @@
 //    the end.  One writer per element, no atomics.
 // NaN among the used columns is outside the contract; the walk clamps every state to [0, 2L] and every code to <= 2, so nothing is read or
 // written out of bounds.  An alias outside [0, V1) reads nothing and counts as -inf.
-#include "common.h"
+#include "host_table.h"
 #include <algorithm>
 #include <vector>
 
@@ -340,7 +340,7 @@ extern "C" int dicow_ctc_forced_align(const void* logits, int in_bf16, int B, in
                                       int blank, const int64_t* table, int n, const int32_t* targets, int64_t n_targets, int32_t* path, int Fmax,
                                       int32_t* spans, int Lmax, float* token_score, float* score, int32_t* status, int plan, void* ws,
                                       int64_t ws_bytes, void* stream) {
-    static thread_local std::vector<int64_t> stage;          // the uploaded image: problems and targets; lives until this thread's next call
+    static thread_local std::vector<int64_t> stage;          // the uploaded image: problems and targets
     ca_plan pl;
     if (ca_make_plan("ctc_forced_align", table, n, plan, &stage, &pl) != DICOW_OK) return DICOW_ERR_INVALID;
     DICOW_REQUIRE(B >= 0 && T >= 0 && V1 > 0 && ld >= V1, "ctc_forced_align: bad logits shape B=%d T=%d V1=%d ld=%lld (ld >= V1 > 0)", B, T, V1, (long long)ld);
@@ -352,10 +352,9 @@ extern "C" int dicow_ctc_forced_align(const void* logits, int in_bf16, int B, in
     for (int k = 0; k < n; ++k) {
         const int64_t* row = table + 5 * (int64_t)k;
         DICOW_REQUIRE(row[0] >= 0 && row[0] < B, "ctc_forced_align: problem %d reads row %lld of logits with B = %d rows", k, (long long)row[0], B);
-        DICOW_REQUIRE(row[1] >= 0 && row[1] <= T && row[2] <= T - row[1], "ctc_forced_align: problem %d reads frames [%lld, %lld + %lld), past the T = %d "
+        DICOW_REQUIRE(dicow_span_ok(row[1], row[2], T), "ctc_forced_align: problem %d reads frames [%lld, %lld + %lld), past the T = %d "
                       "frames of a row", k, (long long)row[1], (long long)row[1], (long long)row[2], T);
-        DICOW_REQUIRE(row[3] >= 0 && row[3] <= n_targets && row[4] <= n_targets - row[3], "ctc_forced_align: problem %d reads targets [%lld, %lld + %lld), "
-                      "outside the %lld ids of the array", k, (long long)row[3], (long long)row[3], (long long)row[4], (long long)n_targets);
+        DICOW_REQUIRE_SPAN(row[3], row[4], n_targets, "reads targets", "ids of the array", "ctc_forced_align: problem %d", k);
         pr[k].row = (int32_t)row[0];
         pr[k].f0 = (int32_t)row[1];
         for (int64_t j = 0; j < row[4]; ++j) {
@@ -369,20 +368,11 @@ extern "C" int dicow_ctc_forced_align(const void* logits, int in_bf16, int B, in
     DICOW_REQUIRE(Fmax >= pl.Fmax && Lmax >= pl.Lmax, "ctc_forced_align: outputs of Fmax=%d frames and Lmax=%d targets, the table needs %d and %d", Fmax,
                   Lmax, pl.Fmax, pl.Lmax);
     DICOW_REQUIRE(logits && path && spans && token_score && score && status && ws, "ctc_forced_align: null pointer");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(logits) % (in_bf16 ? 2 : 4) == 0 && reinterpret_cast<uintptr_t>(lse) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(alias) % 4 == 0 && reinterpret_cast<uintptr_t>(path) % 4 == 0 && reinterpret_cast<uintptr_t>(spans) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(token_score) % 4 == 0 && reinterpret_cast<uintptr_t>(score) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(status) % 4 == 0 && reinterpret_cast<uintptr_t>(ws) % 16 == 0,
+    DICOW_REQUIRE(dicow_aligned(in_bf16 ? 2 : 4, logits) && dicow_aligned(4, lse, alias, path, spans, token_score, score, status) && dicow_aligned(16, ws),
                   "ctc_forced_align: a pointer is not aligned to its element, or ws not 16-byte aligned");
     DICOW_REQUIRE(ws_bytes >= pl.need, "ctc_forced_align: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)pl.need);
     hipStream_t st = (hipStream_t)stream;
-    const void* image = stage.data();
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-    if (cs == hipStreamCaptureStatusActive) image = (new std::vector<int64_t>(stage))->data();      // a graph's copy node reads its source at every
-                                                                                                   // replay: this image is kept for good
-    hipError_t e = hipMemcpyAsync(ws, image, (size_t)pl.table_bytes, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) DICOW_FAIL(DICOW_ERR_LAUNCH, "ctc_forced_align: table upload: %s", hipGetErrorString(e));
+    if (int rc = dicow_upload("ctc_forced_align", ws, stage.data(), pl.table_bytes, st)) return rc;
     ca_args a;
     a.logits = logits; a.lse = lse; a.alias = alias;
     a.probs = reinterpret_cast<const ca_prob*>(ws);

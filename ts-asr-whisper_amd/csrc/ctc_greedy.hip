@@ -18,7 +18,7 @@
 // `>` keeps the first of equal values; the cross-lane steps compare (value, index).  -inf never satisfies `>`: a thread that
 // found nothing above -inf answers with the first column it read, so a row of -inf gives 0.  NaN never satisfies `>` either
 // (outside the contract; the stored index still lies in [0, V1)).
-#include "common.h"
+#include "host_table.h"
 
 #define CGD_BLOCK 256
 #define CGD_NONE 0x7fffffff
@@ -140,7 +140,7 @@ extern "C" int dicow_ctc_greedy_decode(const void* logits, int in_bf16, int64_t 
     DICOW_REQUIRE(B > 0 && Tn > 0 && V1 > 0 && (int64_t)B * Tn < (1ll << 31), "ctc_greedy_decode: bad sizes B=%d Tn=%d V1=%d", B, Tn, V1);
     DICOW_REQUIRE(ld >= V1 && batch_stride >= 0 && out_stride >= Tn, "ctc_greedy_decode: bad strides ld=%lld batch_stride=%lld out_stride=%lld",
                   (long long)ld, (long long)batch_stride, (long long)out_stride);
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(logits) % (in_bf16 ? 2 : 4) == 0, "ctc_greedy_decode: logits not aligned to their element size");
+    DICOW_REQUIRE(dicow_aligned(in_bf16 ? 2 : 4, logits), "ctc_greedy_decode: logits not aligned to their element size");
     const int64_t rows = (int64_t)B * Tn;
     const unsigned grid = (unsigned)(rows < (1 << 20) ? rows : (1 << 20));
     if (in_bf16) ctc_greedy_argmax_kernel<1><<<grid, CGD_BLOCK, 0, (hipStream_t)stream>>>(logits, batch_stride, ld, Tn, V1, rows, ws);

@@ -16,7 +16,7 @@
 //                                 reference's fallback for a speaker who is never alone).
 // Integer arithmetic throughout 1 and 3; every output element has exactly one writer; no atomics; bit-reproducible.
 // The tables are HOST arrays: validated before anything is launched, then copied into the workspace with the stream.
-#include "common.h"
+#include "host_table.h"
 
 #pragma clang fp contract(off)                // every fp32 operation below rounds on its own, as numpy's do
 
@@ -195,14 +195,12 @@ static int dfe_check_targets(const char* who, const int* targets, int n_targets,
     return DICOW_OK;
 }
 
-#define DFE_HIP(call, who) do { hipError_t e_ = (call); if (e_ != hipSuccess) DICOW_FAIL(DICOW_ERR_LAUNCH, "%s: %s", who, hipGetErrorString(e_)); } while (0)
-
 extern "C" int dicow_diar_frame_counts(const int64_t* bounds, const uint64_t* active, int E, int S, int64_t n_samples, int32_t* cnt, int32_t* excl,
                                        void* ws, int64_t ws_bytes, void* stream) {
     DICOW_REQUIRE(E >= 0, "diar_frame_counts: negative E=%d", E);
     if (int rc = dfe_check_sizes("diar_frame_counts", S, n_samples)) return rc;
     DICOW_REQUIRE(bounds && (E == 0 || active) && cnt && excl && ws, "diar_frame_counts: null pointer");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, "diar_frame_counts: ws not 8-byte aligned");
+    DICOW_REQUIRE(dicow_aligned(8, ws), "diar_frame_counts: ws not 8-byte aligned");
     const int64_t need = ((int64_t)2 * E + 1) * 8;
     DICOW_REQUIRE(ws_bytes >= need, "diar_frame_counts: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)need);
     DICOW_REQUIRE(bounds[0] >= 0 && bounds[E] <= n_samples, "diar_frame_counts: bounds [%lld, %lld] outside [0, n_samples=%lld]",
@@ -218,8 +216,8 @@ extern "C" int dicow_diar_frame_counts(const int64_t* bounds, const uint64_t* ac
     hipStream_t st = (hipStream_t)stream;
     int64_t* d_bounds = (int64_t*)ws;
     uint64_t* d_active = (uint64_t*)ws + (E + 1);
-    DFE_HIP(hipMemcpyAsync(d_bounds, bounds, ((int64_t)E + 1) * 8, hipMemcpyHostToDevice, st), "diar_frame_counts: table upload");
-    if (E > 0) DFE_HIP(hipMemcpyAsync(d_active, active, (int64_t)E * 8, hipMemcpyHostToDevice, st), "diar_frame_counts: table upload");
+    if (int rc = dicow_upload("diar_frame_counts", d_bounds, bounds, ((int64_t)E + 1) * 8, st)) return rc;
+    if (int rc = dicow_upload("diar_frame_counts", d_active, active, (int64_t)E * 8, st)) return rc;
     diar_frame_counts_kernel<<<dim3(dicow_cdiv(T_total, DFE_BLOCK), S), DFE_BLOCK, 0, st>>>(d_bounds, d_active, E, T_total, cnt, excl);
     DICOW_CHECK_LAUNCH("diar_frame_counts_kernel");
     return DICOW_OK;
@@ -233,11 +231,11 @@ extern "C" int dicow_stno_from_counts(const int32_t* cnt, int S, int64_t n_sampl
     DICOW_REQUIRE(ld_out >= T_total, "stno_from_counts: ld_out=%lld shorter than T_total=%d", (long long)ld_out, T_total);
     if (n_targets == 0 || T_total == 0) return DICOW_OK;
     DICOW_REQUIRE(cnt && out && ws, "stno_from_counts: null pointer");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, "stno_from_counts: ws not 8-byte aligned");
+    DICOW_REQUIRE(dicow_aligned(8, ws), "stno_from_counts: ws not 8-byte aligned");
     const int64_t need = ((int64_t)n_targets * 4 + 7) / 8 * 8;
     DICOW_REQUIRE(ws_bytes >= need, "stno_from_counts: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)need);
     hipStream_t st = (hipStream_t)stream;
-    DFE_HIP(hipMemcpyAsync(ws, targets, (int64_t)n_targets * 4, hipMemcpyHostToDevice, st), "stno_from_counts: targets upload");
+    if (int rc = dicow_upload("stno_from_counts", ws, targets, (int64_t)n_targets * 4, st)) return rc;
     stno_from_counts_kernel<<<dim3(dicow_cdiv(T_total, DFE_BLOCK), n_targets), DFE_BLOCK, 0, st>>>(cnt, S, T_total, (const int*)ws, out, ld_out);
     DICOW_CHECK_LAUNCH("stno_from_counts_kernel");
     return DICOW_OK;
@@ -255,12 +253,12 @@ extern "C" int dicow_enrollment_windows(const int32_t* cnt, const int32_t* excl,
     DICOW_REQUIRE(!weights || ld_w >= nw, "enrollment_windows: ld_w=%lld shorter than the %d windows", (long long)ld_w, nw);
     if (n_targets == 0) return DICOW_OK;
     DICOW_REQUIRE(cnt && excl && start && count && fallback && ws, "enrollment_windows: null pointer");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, "enrollment_windows: ws not 8-byte aligned");
+    DICOW_REQUIRE(dicow_aligned(8, ws), "enrollment_windows: ws not 8-byte aligned");
     const int64_t tbytes = ((int64_t)n_targets * 4 + 7) / 8 * 8;
     const int64_t need = tbytes + (int64_t)n_targets * (nb64 + 1) * 8;
     DICOW_REQUIRE(ws_bytes >= need, "enrollment_windows: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)need);
     hipStream_t st = (hipStream_t)stream;
-    DFE_HIP(hipMemcpyAsync(ws, targets, (int64_t)n_targets * 4, hipMemcpyHostToDevice, st), "enrollment_windows: targets upload");
+    if (int rc = dicow_upload("enrollment_windows", ws, targets, (int64_t)n_targets * 4, st)) return rc;
     enrollment_windows_kernel<<<n_targets, DFE_BLOCK, 0, st>>>(cnt, excl, (int)dfe_t_total(n_samples), nb, (const int*)ws,
                                                                (int64_t*)((char*)ws + tbytes), start, count, fallback, weights, ld_w);
     DICOW_CHECK_LAUNCH("enrollment_windows_kernel");

@@ -15,7 +15,7 @@
 //                      48 .. 63 and 32 .. 47 of C, which few meetings have).  The chunk's sums go to a partial of 64 Sr + 136 words.
 //   ds_reduce_kernel   one lane per output word: the sum of its partials in ascending chunk order, or 0.
 // No atomics, one writer per word, integers only: the bits do not depend on the chunk size, the grid or the call's other problems.
-#include "common.h"
+#include "host_table.h"
 #include <vector>
 
 #define DS_THREADS 256
@@ -219,10 +219,9 @@ static int ds_check_table(const char* who, int k, const char* side, const int64_
                   who, side, k, (long long)E, DICOW_DIAR_SCORE_MAX_E);
     if (E == 0) return DICOW_OK;                                               // an empty table: nothing of it is read
     DICOW_REQUIRE(bounds && active, "%s: null bounds or active table", who);
-    DICOW_REQUIRE(b0 >= 0 && b0 <= n_bounds && E + 1 <= n_bounds - b0, "%s: the %s table of problem %d reads bounds [%lld, %lld + %lld], outside the "
+    DICOW_REQUIRE(dicow_span_ok(b0, E + 1, n_bounds), "%s: the %s table of problem %d reads bounds [%lld, %lld + %lld], outside the "
                   "%lld of the array", who, side, k, (long long)b0, (long long)b0, (long long)E, (long long)n_bounds);
-    DICOW_REQUIRE(a0 >= 0 && a0 <= n_active && E <= n_active - a0, "%s: the %s table of problem %d reads active [%lld, %lld + %lld), outside the "
-                  "%lld of the array", who, side, k, (long long)a0, (long long)a0, (long long)E, (long long)n_active);
+    DICOW_REQUIRE_SPAN(a0, E, n_active, "reads active", "of the array", "%s: the %s table of problem %d", who, side, k);
     const int64_t* b = bounds + b0;
     const uint64_t* act = active + a0;
     DICOW_REQUIRE(b[0] >= 0 && b[E] <= DICOW_DIAR_SCORE_MAX_TICK, "%s: the %s bounds of problem %d, [%lld, %lld], leave [0, DICOW_DIAR_SCORE_MAX_TICK]",
@@ -261,7 +260,7 @@ static int ds_make_plan(const char* who, const int64_t* bounds, int64_t n_bounds
         const int64_t u0 = row[8], nu = row[9];
         DICOW_REQUIRE(nu >= 0 && nu <= DICOW_DIAR_SCORE_MAX_E, "%s: problem %d has %lld unscored intervals, outside [0, DICOW_DIAR_SCORE_MAX_E = %d]",
                       who, k, (long long)nu, DICOW_DIAR_SCORE_MAX_E);
-        DICOW_REQUIRE(nu == 0 || (unscored && u0 >= 0 && u0 <= n_unscored && nu <= n_unscored - u0), "%s: problem %d reads unscored intervals "
+        DICOW_REQUIRE(nu == 0 || (unscored && dicow_span_ok(u0, nu, n_unscored)), "%s: problem %d reads unscored intervals "
                       "[%lld, %lld + %lld), outside the %lld of the array", who, k, (long long)u0, (long long)u0, (long long)nu, (long long)n_unscored);
         DICOW_REQUIRE((row[10] == 0 || row[10] == 1) && row[11] == 0, "%s: problem %d has skip_overlap=%lld (0 or 1) and reserved=%lld (0)", who, k,
                       (long long)row[10], (long long)row[11]);
@@ -320,12 +319,12 @@ extern "C" int64_t dicow_diar_score_ws_bytes(const int64_t* bounds, int64_t n_bo
 extern "C" int dicow_diar_score(const int64_t* bounds, int64_t n_bounds, const uint64_t* active, int64_t n_active, const int64_t* unscored,
                                 int64_t n_unscored, const int64_t* problems, int n_problems, int chunk, int64_t* out, void* ws, int64_t ws_bytes,
                                 void* stream) {
-    static thread_local ds_plan pl;                          // the descriptors live until this thread's next call
+    static thread_local ds_plan pl;                          // pl.stage: the uploaded descriptors
     if (ds_make_plan("diar_score", bounds, n_bounds, active, n_active, unscored, n_unscored, problems, n_problems, chunk, pl) != DICOW_OK)
         return DICOW_ERR_INVALID;
     if (n_problems == 0) return DICOW_OK;
     DICOW_REQUIRE(out && ws, "diar_score: null pointer");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(out) % 8 == 0 && reinterpret_cast<uintptr_t>(ws) % 8 == 0, "diar_score: out or ws not 8-byte aligned");
+    DICOW_REQUIRE(dicow_aligned(8, out, ws), "diar_score: out or ws not 8-byte aligned");
     DICOW_REQUIRE(ws_bytes >= pl.need, "diar_score: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)pl.need);
     hipStream_t st = (hipStream_t)stream;
     ds_args a;
@@ -335,21 +334,10 @@ extern "C" int dicow_diar_score(const int64_t* bounds, int64_t n_bounds, const u
     a.active = reinterpret_cast<const uint64_t*>(a.bounds + n_bounds);
     a.uns = a.bounds + n_bounds + n_active;
     // four uploads: the descriptors, then the caller's three arrays from where they are
-    const void* src[4] = {pl.stage.data(), bounds, active, unscored};
-    void* dst[4] = {ws, const_cast<int64_t*>(a.bounds), const_cast<uint64_t*>(a.active), const_cast<int64_t*>(a.uns)};
-    const int64_t words[4] = {pl.desc_words, n_bounds, n_active, 2 * n_unscored};
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-    for (int q = 0; q < 4; ++q) {
-        if (words[q] == 0) continue;
-        const void* from = src[q];
-        if (cs == hipStreamCaptureStatusActive) {            // a graph's copy node reads its source at every replay: a copy kept for good
-            const int64_t* w = static_cast<const int64_t*>(from);
-            from = (new std::vector<int64_t>(w, w + words[q]))->data();
-        }
-        hipError_t e = hipMemcpyAsync(dst[q], from, (size_t)words[q] * 8, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) DICOW_FAIL(DICOW_ERR_LAUNCH, "diar_score: table upload: %s", hipGetErrorString(e));
-    }
+    if (int rc = dicow_upload("diar_score", ws, pl.stage.data(), pl.desc_words * 8, st)) return rc;
+    if (int rc = dicow_upload("diar_score", const_cast<int64_t*>(a.bounds), bounds, n_bounds * 8, st)) return rc;
+    if (int rc = dicow_upload("diar_score", const_cast<uint64_t*>(a.active), active, n_active * 8, st)) return rc;
+    if (int rc = dicow_upload("diar_score", const_cast<int64_t*>(a.uns), unscored, n_unscored * 16, st)) return rc;
     a.out = out;
     a.n = n_problems;
     a.chunk = pl.chunk;

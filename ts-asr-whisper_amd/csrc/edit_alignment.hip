@@ -91,107 +91,27 @@ __global__ void __launch_bounds__(64) edit_walk_kernel(const ea_args a) {
     }
 }
 
-// The call's plan, shared by the size query and the entry point: the workgroup width, the key, and the workspace laid out as
-// [n_pairs] ed_pair, [n_pairs] ea_pair, the boundary columns, the records.  image: null, or where to build the uploaded tables.
-static_assert(sizeof(ed_pair) + sizeof(ea_pair) == DICOW_ALIGN_TABLE_BYTES, "the header states the tables' size");
-
-struct ea_plan { int lanes; bool key64, any_ref, any_hyp; int64_t table_bytes, need; };
-
-static inline int64_t ea_rec_bytes(int64_t m, int64_t n, int lanes) {
-    if (m == 0 || n == 0) return 0;
-    const int64_t P = (int64_t)lanes * ED_K, panels = (m + P - 1) / P, w = (m - (panels - 1) * P + ED_K - 1) / ED_K;
-    return (2 * ((panels - 1) * (n + lanes - 1) * lanes + (n + w - 1) * w) + 7) / 8 * 8;
-}
-
-static int ea_make_plan(const char* who, const int64_t* pairs, int n_pairs, int lanes, int along, std::vector<int64_t>* image, ea_plan* plan) {
-    if (ed_check_lens(who, pairs, n_pairs) != DICOW_OK) return DICOW_ERR_INVALID;
-    DICOW_REQUIRE(lanes == 0 || lanes == ED_NARROW || lanes == ED_WIDE, "%s: lanes=%d is none of 0, %d, %d", who, lanes, ED_NARROW, ED_WIDE);
-    DICOW_REQUIRE(along >= 0 && along <= 2, "%s: along=%d is none of 0 (the library's choice), 1 (ref along the lanes), 2 (hyp)", who, along);
-    bool wide = lanes == ED_WIDE;
-    plan->key64 = plan->any_ref = plan->any_hyp = false;
-    for (int k = 0; k < n_pairs; ++k) {
-        const int64_t* row = pairs + 4 * (int64_t)k;
-        if (lanes == 0 && std::min(row[1], row[3]) > (int64_t)ED_NARROW * ED_K) wide = true;
-        plan->key64 |= row[1] + row[3] > ED_I32_MAX_SUM;
-        plan->any_ref |= row[1] > 0;
-        plan->any_hyp |= row[3] > 0;
-    }
-    const int L = plan->lanes = wide ? ED_WIDE : ED_NARROW;
-    plan->table_bytes = (int64_t)n_pairs * (int64_t)(sizeof(ed_pair) + sizeof(ea_pair));
-    if (image) image->assign((size_t)plan->table_bytes / 8, 0);
-    ed_pair* e = image ? reinterpret_cast<ed_pair*>(image->data()) : nullptr;
-    ea_pair* x = image ? reinterpret_cast<ea_pair*>(e + n_pairs) : nullptr;
-    int64_t need = plan->table_bytes, slot = 0;
-    for (int k = 0; k < n_pairs; ++k) {                                         // the boundary columns
-        const int64_t* row = pairs + 4 * (int64_t)k;
-        if (e) e[k].bnd_off = need;
-        need += ed_bnd_bytes(row[1], row[3]);
-    }
-    for (int k = 0; k < n_pairs; ++k) {                                         // the records
-        const int64_t* row = pairs + 4 * (int64_t)k;
-        const bool cols_hyp = along == 2 || (along == 0 && ed_steps(row[3], row[1], L) < ed_steps(row[1], row[3], L));
-        const int64_t m = cols_hyp ? row[3] : row[1], n = cols_hyp ? row[1] : row[3];
-        slot += row[1] + row[3];
-        if (e) {
-            e[k].col_start = cols_hyp ? row[2] : row[0];
-            e[k].row_start = cols_hyp ? row[0] : row[2];
-            e[k].m = (int32_t)m;
-            e[k].n = (int32_t)n;
-            e[k].cols_hyp = cols_hyp;
-            x[k].rec_off = need;
-            x[k].slot_end = slot;
-        }
-        need += ea_rec_bytes(m, n, L);
-        DICOW_REQUIRE(need <= DICOW_ALIGN_MAX_WS_BYTES, "%s: the records up to pair %d of %d bring the workspace to %lld bytes, past "
-                      "DICOW_ALIGN_MAX_WS_BYTES = %lld (split the call)", who, k, n_pairs, (long long)need, (long long)DICOW_ALIGN_MAX_WS_BYTES);
-    }
-    plan->need = need;
-    return DICOW_OK;
-}
-
 extern "C" int64_t dicow_edit_alignment_ws_bytes(const int64_t* pairs, int n_pairs, int lanes, int along) {
-    ea_plan plan;
-    if (ea_make_plan("edit_alignment_ws_bytes", pairs, n_pairs, lanes, along, nullptr, &plan) != DICOW_OK) return -1;
+    ed_plan plan;
+    if (ed_make_plan("edit_alignment_ws_bytes", pairs, n_pairs, lanes, along, true, nullptr, &plan) != DICOW_OK) return -1;
     return plan.need;
-}
-
-template <typename KEY, bool IV>
-static void ea_launch(int lanes, int n_pairs, hipStream_t st, const ea_args& a) {
-    if (lanes == ED_WIDE) edit_distance_kernel<KEY, IV, ED_WIDE, true><<<dim3((unsigned)n_pairs), ED_WIDE, 0, st>>>(a);
-    else edit_distance_kernel<KEY, IV, ED_NARROW, true><<<dim3((unsigned)n_pairs), ED_NARROW, 0, st>>>(a);
 }
 
 extern "C" int dicow_edit_alignment(const int32_t* ref_ids, int64_t n_ref, const int32_t* hyp_ids, int64_t n_hyp, const int32_t* ref_iv,
                                     const int32_t* hyp_iv, const int64_t* pairs, int n_pairs, int32_t* out, uint8_t* ops, int64_t* spans,
                                     int lanes, int along, void* ws, int64_t ws_bytes, void* stream) {
-    static thread_local std::vector<int64_t> stage;          // the uploaded image: both tables; lives until this thread's next call
-    ea_plan plan;
-    if (ea_make_plan("edit_alignment", pairs, n_pairs, lanes, along, &stage, &plan) != DICOW_OK) return DICOW_ERR_INVALID;
-    DICOW_REQUIRE(n_ref >= 0 && n_hyp >= 0, "edit_alignment: negative buffer size n_ref=%lld n_hyp=%lld", (long long)n_ref, (long long)n_hyp);
-    DICOW_REQUIRE((ref_iv == nullptr) == (hyp_iv == nullptr), "edit_alignment: intervals given for one side only (ref_iv %s, hyp_iv %s)",
-                  ref_iv ? "set" : "null", hyp_iv ? "set" : "null");
-    for (int k = 0; k < n_pairs; ++k) {
-        const int64_t* row = pairs + 4 * (int64_t)k;
-        DICOW_REQUIRE(row[0] >= 0 && row[0] <= n_ref && row[1] <= n_ref - row[0], "edit_alignment: pair %d reads ref [%lld, %lld + %lld), outside the %lld "
-                      "ids of the buffer", k, (long long)row[0], (long long)row[0], (long long)row[1], (long long)n_ref);
-        DICOW_REQUIRE(row[2] >= 0 && row[2] <= n_hyp && row[3] <= n_hyp - row[2], "edit_alignment: pair %d reads hyp [%lld, %lld + %lld), outside the %lld "
-                      "ids of the buffer", k, (long long)row[2], (long long)row[2], (long long)row[3], (long long)n_hyp);
-    }
+    static thread_local std::vector<int64_t> stage;          // the uploaded image: both tables
+    ed_plan plan;
+    if (ed_make_plan("edit_alignment", pairs, n_pairs, lanes, along, true, &stage, &plan) != DICOW_OK) return DICOW_ERR_INVALID;
+    if (int rc = ed_check_buffers("edit_alignment", pairs, n_pairs, n_ref, n_hyp, ref_iv, hyp_iv)) return rc;
     if (n_pairs == 0) return DICOW_OK;
     DICOW_REQUIRE(out && spans && ws && (ops || !(plan.any_ref || plan.any_hyp)) && (ref_ids || !plan.any_ref) && (hyp_ids || !plan.any_hyp),
                   "edit_alignment: null pointer");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(ref_ids) % 4 == 0 && reinterpret_cast<uintptr_t>(hyp_ids) % 4 == 0 && reinterpret_cast<uintptr_t>(ref_iv) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(hyp_iv) % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0 && reinterpret_cast<uintptr_t>(spans) % 8 == 0 &&
-                  reinterpret_cast<uintptr_t>(ws) % 8 == 0, "edit_alignment: ids / intervals / out not 4-byte or spans / ws not 8-byte aligned");
+    DICOW_REQUIRE(dicow_aligned(4, ref_ids, hyp_ids, ref_iv, hyp_iv, out) && dicow_aligned(8, spans, ws),
+                  "edit_alignment: ids / intervals / out not 4-byte or spans / ws not 8-byte aligned");
     DICOW_REQUIRE(ws_bytes >= plan.need, "edit_alignment: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)plan.need);
     hipStream_t st = (hipStream_t)stream;
-    const void* image = stage.data();
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-    if (cs == hipStreamCaptureStatusActive) image = (new std::vector<int64_t>(stage))->data();      // a graph's copy node reads its source at every
-                                                                                                   // replay: this image is kept for good
-    hipError_t e = hipMemcpyAsync(ws, image, (size_t)plan.table_bytes, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) DICOW_FAIL(DICOW_ERR_LAUNCH, "edit_alignment: table upload: %s", hipGetErrorString(e));
+    if (int rc = dicow_upload("edit_alignment", ws, stage.data(), plan.table_bytes, st)) return rc;
     ea_args a;
     a.ref_ids = ref_ids; a.hyp_ids = hyp_ids; a.ref_iv = ref_iv; a.hyp_iv = hyp_iv;
     a.pairs = reinterpret_cast<const ed_pair*>(ws);
@@ -200,14 +120,12 @@ extern "C" int dicow_edit_alignment(const int32_t* ref_ids, int64_t n_ref, const
     a.xp = reinterpret_cast<const ea_pair*>(a.pairs + n_pairs);
     a.ops = ops;
     a.spans = spans;
-    const int L = plan.lanes;
     if (EA_ONLY != 2) {
-        if (plan.key64) { if (ref_iv) ea_launch<int64_t, true>(L, n_pairs, st, a); else ea_launch<int64_t, false>(L, n_pairs, st, a); }
-        else { if (ref_iv) ea_launch<int32_t, true>(L, n_pairs, st, a); else ea_launch<int32_t, false>(L, n_pairs, st, a); }
+        ed_launch<true>(plan, n_pairs, st, a);
         DICOW_CHECK_LAUNCH("edit_distance_kernel (recording)");
     }
     if (EA_ONLY != 1) {
-        if (L == ED_WIDE) edit_walk_kernel<ED_WIDE><<<dim3((unsigned)n_pairs), 64, 0, st>>>(a);
+        if (plan.lanes == ED_WIDE) edit_walk_kernel<ED_WIDE><<<dim3((unsigned)n_pairs), 64, 0, st>>>(a);
         else edit_walk_kernel<ED_NARROW><<<dim3((unsigned)n_pairs), 64, 0, st>>>(a);
         DICOW_CHECK_LAUNCH("edit_walk_kernel");
     }

@@ -10,8 +10,9 @@
 // W = the strips of the panel that hold a column <= m (LANES for every panel but the last), so one step's store is one coalesced row of W
 // words.  Only rows 0 <= s - t < n of lanes t < W are written.
 #pragma once
-#include "common.h"
+#include "host_table.h"
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #define ED_K DICOW_EDIT_K
@@ -184,11 +185,20 @@ __global__ void __launch_bounds__(LANES) edit_distance_kernel(const typename ed_
     }
 }
 
+// ---- the host half: one plan and one launcher for both entry points
+static_assert(sizeof(ed_pair) + sizeof(ea_pair) == DICOW_ALIGN_TABLE_BYTES, "the header states the tables' size");
+
 static inline int64_t ed_steps(int64_t m, int64_t n, int lanes) { return (m + (int64_t)lanes * ED_K - 1) / ((int64_t)lanes * ED_K) * (n + lanes - 1); }
 
 static inline int64_t ed_bnd_bytes(int64_t ref_len, int64_t hyp_len) {        // two columns of 8-byte slots when some plan may need a second panel
     const int64_t longer = std::max(ref_len, hyp_len);
     return longer > (int64_t)ED_NARROW * ED_K ? 16 * longer : 0;
+}
+
+static inline int64_t ed_rec_bytes(int64_t m, int64_t n, int lanes) {
+    if (m == 0 || n == 0) return 0;
+    const int64_t P = (int64_t)lanes * ED_K, panels = (m + P - 1) / P, w = (m - (panels - 1) * P + ED_K - 1) / ED_K;
+    return (2 * ((panels - 1) * (n + lanes - 1) * lanes + (n + w - 1) * w) + 7) / 8 * 8;
 }
 
 static inline int ed_check_lens(const char* who, const int64_t* pairs, int n_pairs) {
@@ -202,3 +212,80 @@ static inline int ed_check_lens(const char* who, const int64_t* pairs, int n_pai
     }
     return DICOW_OK;
 }
+
+// The call's plan, shared by the size queries and the entry points: the workgroup width, the key, which sequence of each pair lies along
+// the lanes, and the workspace laid out as [n_pairs] ed_pair, the boundary columns -- or, with rec, as [n_pairs] ed_pair, [n_pairs]
+// ea_pair, the boundary columns, the records.  image: null, or where to build the uploaded tables (the first table_bytes of the workspace).
+struct ed_plan { int lanes; bool key64, any_ref, any_hyp; int64_t table_bytes, need; };
+
+static int ed_make_plan(const char* who, const int64_t* pairs, int n_pairs, int lanes, int along, bool rec, std::vector<int64_t>* image, ed_plan* plan) {
+    if (ed_check_lens(who, pairs, n_pairs) != DICOW_OK) return DICOW_ERR_INVALID;
+    DICOW_REQUIRE(lanes == 0 || lanes == ED_NARROW || lanes == ED_WIDE, "%s: lanes=%d is none of 0, %d, %d", who, lanes, ED_NARROW, ED_WIDE);
+    DICOW_REQUIRE(along >= 0 && along <= 2, "%s: along=%d is none of 0 (the library's choice), 1 (ref along the lanes), 2 (hyp)", who, along);
+    bool wide = lanes == ED_WIDE;
+    plan->key64 = plan->any_ref = plan->any_hyp = false;
+    plan->table_bytes = (int64_t)n_pairs * (int64_t)(sizeof(ed_pair) + (rec ? sizeof(ea_pair) : 0));
+    int64_t need = plan->table_bytes;                                           // behind the boundary columns: where the records begin
+    for (int k = 0; k < n_pairs; ++k) {
+        const int64_t* row = pairs + 4 * (int64_t)k;
+        if (lanes == 0 && std::min(row[1], row[3]) > (int64_t)ED_NARROW * ED_K) wide = true;
+        plan->key64 |= row[1] + row[3] > ED_I32_MAX_SUM;
+        plan->any_ref |= row[1] > 0;
+        plan->any_hyp |= row[3] > 0;
+        need += ed_bnd_bytes(row[1], row[3]);
+    }
+    const int L = plan->lanes = wide ? ED_WIDE : ED_NARROW;
+    plan->need = need;
+    if (!rec && !image) return DICOW_OK;                                        // the counts' size query: nothing more to lay out
+    if (image) image->assign((size_t)plan->table_bytes / 8, 0);
+    ed_pair* e = image ? reinterpret_cast<ed_pair*>(image->data()) : nullptr;
+    ea_pair* x = e && rec ? reinterpret_cast<ea_pair*>(e + n_pairs) : nullptr;
+    int64_t bnd_off = plan->table_bytes, slot = 0;
+    for (int k = 0; k < n_pairs; ++k) {
+        const int64_t* row = pairs + 4 * (int64_t)k;
+        const bool cols_hyp = along == 2 || (along == 0 && ed_steps(row[3], row[1], L) < ed_steps(row[1], row[3], L));
+        const int64_t m = cols_hyp ? row[3] : row[1], n = cols_hyp ? row[1] : row[3];
+        if (e) {
+            e[k].col_start = cols_hyp ? row[2] : row[0];
+            e[k].row_start = cols_hyp ? row[0] : row[2];
+            e[k].m = (int32_t)m;
+            e[k].n = (int32_t)n;
+            e[k].cols_hyp = cols_hyp;
+            e[k].bnd_off = bnd_off;
+        }
+        bnd_off += ed_bnd_bytes(row[1], row[3]);
+        if (!rec) continue;
+        slot += row[1] + row[3];
+        if (x) { x[k].rec_off = need; x[k].slot_end = slot; }
+        need += ed_rec_bytes(m, n, L);
+        DICOW_REQUIRE(need <= DICOW_ALIGN_MAX_WS_BYTES, "%s: the records up to pair %d of %d bring the workspace to %lld bytes, past "
+                      "DICOW_ALIGN_MAX_WS_BYTES = %lld (split the call)", who, k, n_pairs, (long long)need, (long long)DICOW_ALIGN_MAX_WS_BYTES);
+    }
+    plan->need = need;
+    return DICOW_OK;
+}
+
+// What both entry points refuse once the plan stands: bad id buffers, a pair that reads past them.
+static int ed_check_buffers(const char* who, const int64_t* pairs, int n_pairs, int64_t n_ref, int64_t n_hyp, const int32_t* ref_iv, const int32_t* hyp_iv) {
+    if (int rc = dicow_check_id_buffers(who, n_ref, n_hyp, ref_iv, hyp_iv)) return rc;
+    for (int k = 0; k < n_pairs; ++k) {
+        const int64_t* row = pairs + 4 * (int64_t)k;
+        DICOW_REQUIRE_SPAN(row[0], row[1], n_ref, "reads ref", "ids of the buffer", "%s: pair %d", who, k);
+        DICOW_REQUIRE_SPAN(row[2], row[3], n_hyp, "reads hyp", "ids of the buffer", "%s: pair %d", who, k);
+    }
+    return DICOW_OK;
+}
+
+// The table kernel of the plan: key width x intervals x lanes.
+template <bool REC>
+static void ed_launch(const ed_plan& plan, int n_pairs, hipStream_t st, const typename ed_args_of<REC>::type& a) {
+    auto go = [&](auto key, auto iv) {
+        using KEY = decltype(key);
+        constexpr bool IV = decltype(iv)::value;
+        if (plan.lanes == ED_WIDE) edit_distance_kernel<KEY, IV, ED_WIDE, REC><<<dim3((unsigned)n_pairs), ED_WIDE, 0, st>>>(a);
+        else edit_distance_kernel<KEY, IV, ED_NARROW, REC><<<dim3((unsigned)n_pairs), ED_NARROW, 0, st>>>(a);
+    };
+    if (plan.key64) { if (a.ref_iv) go(int64_t{}, std::true_type{}); else go(int64_t{}, std::false_type{}); }
+    else { if (a.ref_iv) go(int32_t{}, std::true_type{}); else go(int32_t{}, std::false_type{}); }
+}
+

@@ -1,6 +1,7 @@
 // Error plumbing + small HBM-bound helper kernels (casts, layout packs, column sums).
 #include <stdarg.h>
-#include "common.h"
+#include <new>
+#include "host_table.h"
 
 static thread_local char g_err[512] = "";
 
@@ -9,6 +10,16 @@ void dicow_set_error(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+int dicow_upload(const char* who, void* dst, const void* src, int64_t bytes, hipStream_t stream) {
+    if (bytes == 0) return DICOW_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) (void)hipGetLastError();
+    if (cs == hipStreamCaptureStatusActive) src = memcpy(::operator new((size_t)bytes), src, (size_t)bytes);   // kept for good: host_table.h
+    hipError_t e = hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) DICOW_FAIL(DICOW_ERR_LAUNCH, "%s: table upload: %s", who, hipGetErrorString(e));
+    return DICOW_OK;
 }
 
 extern "C" int dicow_abi_version(void) { return DICOW_ABI_VERSION; }

@@ -11,7 +11,7 @@
 // __fadd_rn; a sample no track covers is stored as 0.  Each sample of [0, n) has exactly one writer and is written once -- float4 stores,
 // single stores on the up-to-three samples behind the last whole vector -- so the sum of a sample is a function of the plan alone: no
 // atomics, no workspace, no dependence on the grid.  The plan is validated on the host before the launch (dicow_enrollment_mix).
-#include "common.h"
+#include "host_table.h"
 
 #define EMX_BLOCK 256
 #define EMX_VPT 4                         // vectors per thread
@@ -113,9 +113,8 @@ extern "C" int dicow_enrollment_mix(float* out, int64_t ld_out, int B, int n, co
     }
     if (B == 0 || n == 0) return DICOW_OK;
     DICOW_REQUIRE(out && (n_tracks == 0 || (bank && clip_start && plan_dev)), "enrollment_mix: null pointer");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "enrollment_mix: out not 16-byte aligned");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(bank) % 4 == 0 && reinterpret_cast<uintptr_t>(plan_dev) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(clip_start) % 8 == 0, "enrollment_mix: bank / plan / clip_start misaligned");
+    DICOW_REQUIRE(dicow_aligned(16, out), "enrollment_mix: out not 16-byte aligned");
+    DICOW_REQUIRE(dicow_aligned(4, bank, plan_dev) && dicow_aligned(8, clip_start), "enrollment_mix: bank / plan / clip_start misaligned");
     const int nvec = (n + 3) >> 2;
     const dim3 grid(dicow_cdiv(nvec, EMX_BLOCK * EMX_VPT), B);
     enrollment_mix_kernel<<<grid, EMX_BLOCK, 0, (hipStream_t)stream>>>(out, ld_out, n, bank, clip_start, plan_dev, n_tracks);

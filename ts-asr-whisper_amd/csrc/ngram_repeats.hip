@@ -27,7 +27,7 @@
 //    and reason.
 // No atomics, one writer per element, no waiting between workgroups; one copy (the tables, into ws, on the stream) and two launches, no
 // host read: the call can be captured into a graph.  Results depend neither on the plan nor on the other segments.
-#include "common.h"
+#include "host_table.h"
 #include <algorithm>
 #include <vector>
 
@@ -216,7 +216,7 @@ extern "C" int dicow_ngram_repeats(const int32_t* ids, const int32_t* fold, int6
     DICOW_REQUIRE(unigram_min_repeat >= 1, "ngram_repeats: unigram_min_repeat=%d, must be >= 1", unigram_min_repeat);
     DICOW_REQUIRE(repeat_threshold >= 0, "ngram_repeats: repeat_threshold=%d, must be >= 0", repeat_threshold);
     // ---- the segment and work item tables, on the host, before anything is launched
-    static thread_local std::vector<int64_t> stage;          // the uploaded image: segments, then items; lives until this thread's next call
+    static thread_local std::vector<int64_t> stage;          // the uploaded image: segments, then items
     stage.assign((size_t)(((int64_t)n * DICOW_NGRAM_SEG_BYTES + pl.items * DICOW_NGRAM_ITEM_BYTES) / 8), 0);
     nr_seg* sg = reinterpret_cast<nr_seg*>(stage.data());
     nr_item* it = reinterpret_cast<nr_item*>(sg + n);
@@ -225,8 +225,7 @@ extern "C" int dicow_ngram_repeats(const int32_t* ids, const int32_t* fold, int6
     bool any = false;
     for (int k = 0; k < n; ++k) {
         const int64_t start = table[2 * (int64_t)k], W = table[2 * (int64_t)k + 1];
-        DICOW_REQUIRE(start >= 0 && start <= n_words && W <= n_words - start, "ngram_repeats: segment %d reads words [%lld, %lld + %lld), outside the %lld "
-                      "ids of the buffer", k, (long long)start, (long long)start, (long long)W, (long long)n_words);
+        DICOW_REQUIRE_SPAN(start, W, n_words, "reads words", "ids of the buffer", "ngram_repeats: segment %d", k);
         any |= W > 0;
         sg[k].start = start;
         sg[k].W = (int32_t)W;
@@ -238,19 +237,12 @@ extern "C" int dicow_ngram_repeats(const int32_t* ids, const int32_t* fold, int6
     }
     if (n == 0) return DICOW_OK;
     DICOW_REQUIRE(keep && ws && ((ids && fold) || !any), "ngram_repeats: null pointer");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(ids) % 4 == 0 && reinterpret_cast<uintptr_t>(fold) % 4 == 0 && reinterpret_cast<uintptr_t>(keep) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(reason) % 4 == 0 && reinterpret_cast<uintptr_t>(ws) % 16 == 0,
+    DICOW_REQUIRE(dicow_aligned(4, ids, fold, keep, reason) && dicow_aligned(16, ws),
                   "ngram_repeats: ids / fold / keep / reason not 4-byte or ws not 16-byte aligned");
     DICOW_REQUIRE(ws_bytes >= pl.need, "ngram_repeats: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)pl.need);
     hipStream_t st = (hipStream_t)stream;
     const int64_t tbytes = (int64_t)n * DICOW_NGRAM_SEG_BYTES + items * DICOW_NGRAM_ITEM_BYTES;
-    const void* image = stage.data();
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-    if (cs == hipStreamCaptureStatusActive) image = (new std::vector<int64_t>(stage))->data();      // a graph's copy node reads its source at every
-                                                                                                   // replay: this image is kept for good
-    hipError_t e = hipMemcpyAsync(ws, image, (size_t)tbytes, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) DICOW_FAIL(DICOW_ERR_LAUNCH, "ngram_repeats: table upload: %s", hipGetErrorString(e));
+    if (int rc = dicow_upload("ngram_repeats", ws, stage.data(), tbytes, st)) return rc;
     nr_args a;
     a.ids = ids; a.fold = fold;
     a.segs = reinterpret_cast<const nr_seg*>(ws);

@@ -18,7 +18,7 @@
 // both [0, len) and the clip; the up-to-three samples behind the last whole vector of a row, and vectors that straddle the end of the
 // clip, go element by element.  Nothing outside [0, len) of a row is written, nothing outside the clip is read.
 // out == wave is legal: pass 1 only reads, and pass 2 reads each sample in the thread that then writes it.
-#include "common.h"
+#include "host_table.h"
 
 #define NMX_BLOCK 256
 #define NMX_PARTS 64                     // partial slots per row = lanes of the re-sum butterfly
@@ -178,8 +178,8 @@ extern "C" int dicow_noise_mix(const float* wave, int64_t ld_wave, float* out, i
     DICOW_REQUIRE(n_plan <= 65535, "noise_mix: n_plan=%d exceeds 65535 rows per call", n_plan);
     DICOW_REQUIRE(ld_wave >= 0 && ld_out >= 0 && ld_wave % 4 == 0 && ld_out % 4 == 0, "noise_mix: row strides must be non-negative multiples of 4 "
                   "(ld_wave=%lld ld_out=%lld)", (long long)ld_wave, (long long)ld_out);
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(wave) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0, "noise_mix: wave / out not 16-byte aligned");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(bank) % 4 == 0 && reinterpret_cast<uintptr_t>(ws) % 8 == 0, "noise_mix: bank / ws misaligned");
+    DICOW_REQUIRE(dicow_aligned(16, wave, out), "noise_mix: wave / out not 16-byte aligned");
+    DICOW_REQUIRE(dicow_aligned(4, bank) && dicow_aligned(8, ws), "noise_mix: bank / ws misaligned");
     DICOW_REQUIRE(out != wave || ld_out == ld_wave, "noise_mix: in place (out == wave) needs ld_out == ld_wave");
     DICOW_REQUIRE(ws_bytes >= (int64_t)n_plan * NMX_SLOT_BYTES, "noise_mix: ws_bytes=%lld, need %lld", (long long)ws_bytes,
                   (long long)((int64_t)n_plan * NMX_SLOT_BYTES));

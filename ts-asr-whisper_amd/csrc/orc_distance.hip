@@ -22,7 +22,7 @@
 // entered it, so min() also picks the smallest origin among equal keys; orc_fold_kernel takes the stream with the smallest index among
 // equal keys and stores (axis << 16 | origin) per cell per step; orc_finish_kernel chases U such records back from the corner.  (errors,
 // hits) are the same with and without.  No atomics, no wait on another workgroup: steps are ordered by launch order on the stream.
-#include "common.h"
+#include "host_table.h"
 #include <algorithm>
 #include <vector>
 
@@ -270,8 +270,7 @@ static int orc_make_plan(const char* who, const int64_t* problems, int n, const 
             DICOW_REQUIRE(r[1] >= 0, "%s: utterance %d of problem %d has a negative length %lld", who, u, k, (long long)r[1]);
             DICOW_REQUIRE(r[1] <= DICOW_ORC_MAX_WORDS, "%s: utterance %d of problem %d has %lld words, more than DICOW_ORC_MAX_WORDS = %d", who, u, k,
                           (long long)r[1], DICOW_ORC_MAX_WORDS);
-            DICOW_REQUIRE(!spans || (r[0] >= 0 && r[0] <= n_ref && r[1] <= n_ref - r[0]), "%s: utterance %d of problem %d reads ref [%lld, %lld + %lld), "
-                          "outside the %lld ids of the buffer", who, u, k, (long long)r[0], (long long)r[0], (long long)r[1], (long long)n_ref);
+            if (spans) DICOW_REQUIRE_SPAN(r[0], r[1], n_ref, "reads ref", "ids of the buffer", "%s: utterance %d of problem %d", who, u, k);
             ut[utt0 + u].ref_start = r[0];
             ut[utt0 + u].len = (int32_t)r[1];
             ut[utt0 + u].row = (int32_t)(row[0] + u);
@@ -285,8 +284,7 @@ static int orc_make_plan(const char* who, const int64_t* problems, int n, const 
             DICOW_REQUIRE(r[1] >= 0, "%s: stream %d of problem %d has a negative length %lld", who, h, k, (long long)r[1]);
             DICOW_REQUIRE(r[1] <= DICOW_ORC_MAX_WORDS, "%s: stream %d of problem %d has %lld words, more than DICOW_ORC_MAX_WORDS = %d", who, h, k,
                           (long long)r[1], DICOW_ORC_MAX_WORDS);
-            DICOW_REQUIRE(!spans || (r[0] >= 0 && r[0] <= n_hyp && r[1] <= n_hyp - r[0]), "%s: stream %d of problem %d reads hyp [%lld, %lld + %lld), "
-                          "outside the %lld ids of the buffer", who, h, k, (long long)r[0], (long long)r[0], (long long)r[1], (long long)n_hyp);
+            if (spans) DICOW_REQUIRE_SPAN(r[0], r[1], n_hyp, "reads hyp", "ids of the buffer", "%s: stream %d of problem %d", who, h, k);
             hyp_words += r[1];
             axes[h] = h;
         }
@@ -363,10 +361,8 @@ static void orc_launch(const orc_plan& pl, int n, hipStream_t st, const orc_args
 extern "C" int dicow_orc_distance(const int32_t* ref_ids, int64_t n_ref, const int32_t* hyp_ids, int64_t n_hyp, const int32_t* ref_iv,
                                   const int32_t* hyp_iv, const int64_t* problems, int n_problems, const int64_t* utts, const int64_t* streams,
                                   int32_t* out, int32_t* assignment, void* ws, int64_t ws_bytes, void* stream) {
-    DICOW_REQUIRE(n_ref >= 0 && n_hyp >= 0, "orc_distance: negative buffer size n_ref=%lld n_hyp=%lld", (long long)n_ref, (long long)n_hyp);
-    DICOW_REQUIRE((ref_iv == nullptr) == (hyp_iv == nullptr), "orc_distance: intervals given for one side only (ref_iv %s, hyp_iv %s)",
-                  ref_iv ? "set" : "null", hyp_iv ? "set" : "null");
-    static thread_local orc_plan pl;                         // the uploaded image lives until this thread's next call
+    if (int rc = dicow_check_id_buffers("orc_distance", n_ref, n_hyp, ref_iv, hyp_iv)) return rc;
+    static thread_local orc_plan pl;                         // pl.stage is the uploaded image
     if (orc_make_plan("orc_distance", problems, n_problems, utts, streams, assignment != nullptr, n_ref, n_hyp, pl) != DICOW_OK)
         return DICOW_ERR_INVALID;
     if (n_problems == 0) return DICOW_OK;
@@ -379,18 +375,11 @@ extern "C" int dicow_orc_distance(const int32_t* ref_ids, int64_t n_ref, const i
         for (int u = 0; u < probs[q].U; ++u) any_ref |= ut[probs[q].utt0 + u].len > 0;
     }
     DICOW_REQUIRE(out && ws && (ref_ids || !any_ref) && (hyp_ids || !any_hyp), "orc_distance: null pointer");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(ref_ids) % 4 == 0 && reinterpret_cast<uintptr_t>(hyp_ids) % 4 == 0 && reinterpret_cast<uintptr_t>(ref_iv) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(hyp_iv) % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0 && reinterpret_cast<uintptr_t>(assignment) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(ws) % 8 == 0, "orc_distance: ids / intervals / out / assignment not 4-byte or ws not 8-byte aligned");
+    DICOW_REQUIRE(dicow_aligned(4, ref_ids, hyp_ids, ref_iv, hyp_iv, out, assignment) && dicow_aligned(8, ws),
+                  "orc_distance: ids / intervals / out / assignment not 4-byte or ws not 8-byte aligned");
     DICOW_REQUIRE(ws_bytes >= pl.need, "orc_distance: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)pl.need);
     hipStream_t st = (hipStream_t)stream;
-    const void* image = pl.stage.data();
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-    if (cs == hipStreamCaptureStatusActive) image = (new std::vector<int64_t>(pl.stage))->data();   // a graph's copy node reads its source at
-                                                                                                   // every replay: this image is kept for good
-    hipError_t e = hipMemcpyAsync(ws, image, (size_t)pl.head_bytes, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) DICOW_FAIL(DICOW_ERR_LAUNCH, "orc_distance: table upload: %s", hipGetErrorString(e));
+    if (int rc = dicow_upload("orc_distance", ws, pl.stage.data(), pl.head_bytes, st)) return rc;
     orc_args a;
     a.ref_ids = ref_ids; a.hyp_ids = hyp_ids; a.ref_iv = ref_iv; a.hyp_iv = hyp_iv;
     a.probs = reinterpret_cast<const orc_prob*>(ws);

@@ -21,7 +21,7 @@
 //      with the same phase read the span o apart), and for each output  acc = 0; for s ascending: acc = fmaf(taps[p][s], x[..], acc).
 // Every output sample has one writer and its sum has one order, so its bits do not depend on F, the grid, or what else is in the table.
 // No atomics; the workspace holds the uploaded segment table and first[] only; one launch, capturable.  All sample positions are int64.
-#include "common.h"
+#include "host_table.h"
 #include <algorithm>
 #include <vector>
 
@@ -234,7 +234,7 @@ extern "C" int dicow_resample(const void* in, int in_int16, int C, int channel, 
     DICOW_REQUIRE(F * n <= (1 << 30), "resample: frames_per_tile=%d makes tiles of more than 2^30 samples (n=%d)", frames_per_tile, n);
     // ---- the segment table, on the host, before anything is launched
     DICOW_REQUIRE(n_segs == 0 || segs, "resample: null segment table");
-    static thread_local std::vector<int64_t> stage;          // the uploaded image: [n_segs] rsm_seg, then first[n]; lives until this thread's next call
+    static thread_local std::vector<int64_t> stage;          // the uploaded image: [n_segs] rsm_seg, then first[n]
     static thread_local std::vector<std::pair<int64_t, int64_t>> spans;
     const int64_t tbytes = (int64_t)n_segs * (int64_t)sizeof(rsm_seg);
     stage.assign((size_t)((tbytes + rsm_first_bytes(n)) / 8), 0);
@@ -242,11 +242,10 @@ extern "C" int dicow_resample(const void* in, int in_int16, int C, int channel, 
     int64_t tiles = 0;
     for (int k = 0; k < n_segs; ++k) {
         const int64_t in_start = segs[3 * (int64_t)k], in_len = segs[3 * (int64_t)k + 1], out_start = segs[3 * (int64_t)k + 2];
-        DICOW_REQUIRE(in_len >= 0 && in_start >= 0 && in_start <= in_frames && in_len <= in_frames - in_start, "resample: segment %d reads [%lld, %lld + %lld), "
-                      "outside the %lld frames of the input", k, (long long)in_start, (long long)in_start, (long long)in_len, (long long)in_frames);
+        DICOW_REQUIRE(in_len >= 0, "resample: segment %d has the negative input length %lld", k, (long long)in_len);
+        DICOW_REQUIRE_SPAN(in_start, in_len, in_frames, "reads", "frames of the input", "resample: segment %d", k);
         const int64_t out_len = (n * in_len + o - 1) / o;    // (in_len < 2^63 / 2^20 is implied by any real buffer)
-        DICOW_REQUIRE(out_start >= 0 && out_start <= out_samples && out_len <= out_samples - out_start, "resample: segment %d writes [%lld, %lld + %lld), "
-                      "outside the %lld samples of the output", k, (long long)out_start, (long long)out_start, (long long)out_len, (long long)out_samples);
+        DICOW_REQUIRE_SPAN(out_start, out_len, out_samples, "writes", "samples of the output", "resample: segment %d", k);
         if (out_len > 0) spans.emplace_back(out_start, out_start + out_len);
         int64_t* row = stage.data() + 4 * (int64_t)k;
         row[0] = in_start; row[1] = in_len; row[2] = out_start; row[3] = tiles;
@@ -260,16 +259,13 @@ extern "C" int dicow_resample(const void* in, int in_int16, int C, int channel, 
                       (long long)spans[k - 1].first, (long long)spans[k - 1].second, (long long)spans[k].first, (long long)spans[k].second);
     if (tiles == 0) return DICOW_OK;
     DICOW_REQUIRE(in && out && taps_t && ws, "resample: null pointer");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(in) % (in_int16 ? 2 : 4) == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0, "resample: in / out not aligned "
-                  "to their element size");
-    DICOW_REQUIRE(reinterpret_cast<uintptr_t>(taps_t) % 16 == 0 && reinterpret_cast<uintptr_t>(ws) % 8 == 0, "resample: taps_t not 16-byte or ws not "
-                  "8-byte aligned");
+    DICOW_REQUIRE(dicow_aligned(in_int16 ? 2 : 4, in) && dicow_aligned(4, out), "resample: in / out not aligned to their element size");
+    DICOW_REQUIRE(dicow_aligned(16, taps_t) && dicow_aligned(8, ws), "resample: taps_t not 16-byte or ws not 8-byte aligned");
     const int64_t need = tbytes + rsm_first_bytes(n);
     DICOW_REQUIRE(ws_bytes >= need, "resample: ws_bytes=%lld, need %lld", (long long)ws_bytes, (long long)need);
     memcpy(reinterpret_cast<char*>(stage.data()) + tbytes, first, (size_t)n * 4);
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(ws, stage.data(), (size_t)need, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) DICOW_FAIL(DICOW_ERR_LAUNCH, "resample: table upload: %s", hipGetErrorString(e));
+    if (int rc = dicow_upload("resample", ws, stage.data(), need, st)) return rc;
     rsm_args a;
     a.in = in; a.out = out; a.taps_t = taps_t;
     a.segs = reinterpret_cast<const rsm_seg*>(ws);
@@ -278,7 +274,7 @@ extern "C" int dicow_resample(const void* in, int in_int16, int C, int channel, 
     a.lo = fmin - width; a.fmin = fmin; a.D = D;
     a.xs_floats = (int)(((F - 1) * o + D + S + 8 + 3) / 4 * 4);
     const size_t lds_bytes = ((size_t)a.xs_floats + (taps_lds ? (size_t)S * n : 0)) * 4;
-    const int mode = !in_int16 ? RSM_F32 : C == 1 ? RSM_I16_MONO : (C == 2 && channel < 0 && reinterpret_cast<uintptr_t>(in) % 4 == 0) ? RSM_I16_STEREO : RSM_I16_ANY;
+    const int mode = !in_int16 ? RSM_F32 : C == 1 ? RSM_I16_MONO : (C == 2 && channel < 0 && dicow_aligned(4, in)) ? RSM_I16_STEREO : RSM_I16_ANY;
     switch (mode) {
         case RSM_F32: rsm_launch<RSM_F32>(taps_lds, tiles, lds_bytes, st, a); break;
         case RSM_I16_MONO: rsm_launch<RSM_I16_MONO>(taps_lds, tiles, lds_bytes, st, a); break;

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import ops
 from .ctc_decoding import chunked_ctc_logits
 
 F32, BF16, I32 = torch.float32, torch.bfloat16, torch.int32
@@ -48,11 +49,10 @@ def _host_ints(x, n, name, default):
 
 
 def _groups(lib, table):
-    """Runs of problems whose workspaces fit DICOW_CTC_ALIGN_MAX_WS_BYTES: [(first, last + 1, bytes)].  Normally one."""
+    """Runs of problems whose workspaces fit DICOW_CTC_ALIGN_MAX_WS_BYTES: [(first, last + 1)].  Normally one."""
     n = len(table)
-    need = lib.dicow_ctc_align_ws_bytes(table.ctypes.data if n else None, n)
-    if need >= 0:
-        return [(0, n, need)]
+    if lib.dicow_ctc_align_ws_bytes(table.ctypes.data if n else None, n) >= 0:
+        return [(0, n)]
     out, first, acc = [], 0, 0
     for k in range(n):
         one = lib.dicow_ctc_align_ws_bytes(table[k:k + 1].ctypes.data, 1)
@@ -63,7 +63,7 @@ def _groups(lib, table):
             first, acc = k, 0
         acc += one
     out.append((first, n))
-    return [(a, b, lib.dicow_ctc_align_ws_bytes(table[a:b].ctypes.data, b - a)) for a, b in out]
+    return out
 
 
 def ctc_forced_align(logits, targets, target_lengths=None, *, blank, rows=None, frame_start=None, frame_len=None, alias=None, lse=None,
@@ -133,11 +133,9 @@ def ctc_forced_align(logits, targets, target_lengths=None, *, blank, rows=None, 
             raise L.DicowError(f"ctc_forced_align: lse must hold B * T = {B * T} values on the GPU")
         lse = lse.to(F32).contiguous()
     lib = L.lib()
-    for a, b, need in _groups(lib, table):
-        if need < 0:
-            raise L.DicowError(f"ctc_forced_align: {lib.dicow_last_error().decode()}")
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    for a, b in _groups(lib, table):
         sub = np.ascontiguousarray(table[a:b])
+        ws, _ = ops.table_workspace("ctc_forced_align", lib.dicow_ctc_align_ws_bytes, sub.ctypes.data, b - a, device=dev, pooled=False)
         L.call("dicow_ctc_forced_align", logits.data_ptr(), int(logits.dtype == BF16), B, T, V1, ld, L.ptr(lse), L.ptr(alias), int(blank),
                sub.ctypes.data, b - a, flat.ctypes.data if flat.size else None, flat.size, out.path[a:].data_ptr(), Fmax,
                out.spans[a:].data_ptr(), Lmax, out.token_score[a:].data_ptr(), out.score[a:].data_ptr(), status[a:].data_ptr(), int(plan),

@@ -73,10 +73,7 @@ def diar_score_counts(problems, chunk: int = 0, device="cuda", out=None) -> torc
     dev = out.device
     tables = table_args(b, a, u, pt, chunk)
     with torch.cuda.device(dev):
-        nbytes = L.lib().dicow_diar_score_ws_bytes(*tables)
-        if nbytes < 0:
-            raise L.DicowError(f"diar_score_counts: {L.lib().dicow_last_error().decode()}")
-        ws = ops.workspace(nbytes, dev)
+        ws, nbytes = ops.table_workspace("diar_score_counts", L.lib().dicow_diar_score_ws_bytes, *tables, device=dev)
         L.call("dicow_diar_score", *tables, out.data_ptr(), ws.data_ptr(), nbytes, L.stream())
     diar_score_counts._tables = (b, a, u, pt)                        # (kept: the stream may read the host arrays after the call returns)
     return out

@@ -49,11 +49,8 @@ def repeating_ngram_cuts(ids: torch.Tensor, fold_ids: torch.Tensor, table, *, mi
     keep = torch.empty(n, dtype=torch.int32, device=ids.device)
     reason = torch.empty((n, 3), dtype=torch.int32, device=ids.device)
     with torch.cuda.device(ids.device):
-        lib = L.lib()
-        nbytes = lib.dicow_ngram_repeats_ws_bytes(table.ctypes.data if n else None, n, plan)
-        if nbytes < 0:
-            raise L.DicowError(f"repeating_ngram_cuts: {lib.dicow_last_error().decode()}")
-        ws = ops.workspace(nbytes, ids.device)
+        ws, nbytes = ops.table_workspace("repeating_ngram_cuts", L.lib().dicow_ngram_repeats_ws_bytes, table.ctypes.data if n else None, n, plan,
+                                         device=ids.device)
         L.call("dicow_ngram_repeats", ids.data_ptr(), fold_ids.data_ptr(), ids.numel(), table.ctypes.data if n else None, n, int(min_n), int(max_n),
                int(min_word_threshold), int(unigram_min_repeat), int(repeat_threshold), keep.data_ptr(), reason.data_ptr(), plan, ws.data_ptr(),
                nbytes, L.stream())

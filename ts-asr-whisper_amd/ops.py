@@ -41,6 +41,16 @@ def workspace(nbytes: int, device) -> torch.Tensor:
     return t
 
 
+def table_workspace(who: str, size_fn, *args, device, pooled: bool = True):
+    """The size query of a table-driven entry point (``size_fn``: its ``dicow_*_ws_bytes``), then the workspace: ``(ws, nbytes)``.  A
+    negative size is the library's refusal of the tables: raised with its message.  ``pooled=False``: a buffer of the call's own, for
+    sizes that should not stay in the per-device pool."""
+    nbytes = size_fn(*args)
+    if nbytes < 0:
+        raise L.DicowError(f"{who}: {L.lib().dicow_last_error().decode()}")
+    return (workspace(nbytes, device) if pooled else torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)), nbytes
+
+
 def gemm_dispatch_log() -> dict:
     """{kernel instantiation name (as rocprofv3 prints it): launches so far in this process} (dicow_gemm_dispatch_log)."""
     n = L.lib().dicow_gemm_dispatch_log(None, 0)

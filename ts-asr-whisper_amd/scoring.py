@@ -66,7 +66,7 @@ _TIMESTAMP = re.compile(r"\<\|\d+\.\d+\|\>")
 
 
 def _check_edit_inputs(who: str, ref_ids, hyp_ids, ref_iv, hyp_iv):
-    """The refusals ``edit_counts`` and ``edit_alignments`` share: flat contiguous int32 ids on one GPU, intervals for both sides or neither."""
+    """The refusals ``edit_counts``, ``edit_alignments`` and ``orc_counts`` share: flat contiguous int32 ids on one GPU, intervals for both sides or neither."""
     for t, name in ((ref_ids, "ref_ids"), (hyp_ids, "hyp_ids")):
         if not torch.is_tensor(t) or not t.is_cuda:
             raise L.DicowError(f"{who}: {name} must be on the GPU (no CPU fallback)")
@@ -98,10 +98,8 @@ def edit_counts(ref_ids: torch.Tensor, hyp_ids: torch.Tensor, pairs, ref_iv: Opt
           or not out.is_contiguous()):
         raise L.DicowError(f"edit_counts: out must be a contiguous int32 [{n}, 2] tensor on {ref_ids.device}")
     with torch.cuda.device(ref_ids.device):
-        nbytes = L.lib().dicow_edit_distance_ws_bytes(table.ctypes.data if n else None, n)
-        if nbytes < 0:
-            raise L.DicowError(f"edit_counts: {L.lib().dicow_last_error().decode()}")
-        ws = ops.workspace(nbytes, ref_ids.device)
+        ws, nbytes = ops.table_workspace("edit_counts", L.lib().dicow_edit_distance_ws_bytes, table.ctypes.data if n else None, n,
+                                         device=ref_ids.device)
         L.call("dicow_edit_distance", ref_ids.data_ptr(), ref_ids.numel(), hyp_ids.data_ptr(), hyp_ids.numel(), L.ptr(ref_iv), L.ptr(hyp_iv),
                table.ctypes.data if n else None, n, out.data_ptr(), int(lanes), int(along), ws.data_ptr(), nbytes, L.stream())
     return counts_from(out.cpu(), table)
@@ -368,19 +366,7 @@ def orc_counts(ref_ids: torch.Tensor, hyp_ids: torch.Tensor, problems, utts, str
     CPU, ``(errors, hits, substitutions, deletions, insertions)`` per problem; with ``want_assignment`` also an int32 tensor with one
     entry per row of ``utts``: the stream within its problem the utterance was given to (-1: the problem has no stream, or no problem
     names the row).  ``out``: a contiguous int32 ``[n, 2]`` device tensor to receive ``(errors, hits)``."""
-    for t, name in ((ref_ids, "ref_ids"), (hyp_ids, "hyp_ids")):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise L.DicowError(f"orc_counts: {name} must be on the GPU (no CPU fallback)")
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
-            raise L.DicowError(f"orc_counts: {name} must be a flat contiguous int32 tensor")
-    if hyp_ids.device != ref_ids.device:
-        raise L.DicowError("orc_counts: ref_ids and hyp_ids are on different devices")
-    if (ref_iv is None) != (hyp_iv is None):
-        raise L.DicowError("orc_counts: intervals must be given for both sides or for neither")
-    for iv, ids, name in ((ref_iv, ref_ids, "ref_iv"), (hyp_iv, hyp_ids, "hyp_iv")):
-        if iv is not None and (not torch.is_tensor(iv) or iv.device != ids.device or iv.dtype != torch.int32 or tuple(iv.shape) != (ids.numel(), 2)
-                               or not iv.is_contiguous()):
-            raise L.DicowError(f"orc_counts: {name} must be a contiguous int32 [{ids.numel()}, 2] tensor on {ids.device}")
+    _check_edit_inputs("orc_counts", ref_ids, hyp_ids, ref_iv, hyp_iv)
     pt = np.ascontiguousarray(np.asarray(problems, dtype=np.int64).reshape(-1, 4))
     ut = np.ascontiguousarray(np.asarray(utts, dtype=np.int64).reshape(-1, 2))
     st = np.ascontiguousarray(np.asarray(streams, dtype=np.int64).reshape(-1, 2))
@@ -395,10 +381,7 @@ def orc_counts(ref_ids: torch.Tensor, hyp_ids: torch.Tensor, problems, utts, str
     asg = torch.full((max(len(ut), 1),), -1, dtype=torch.int32, device=dev) if want_assignment else None
     tables = (pt.ctypes.data if n else None, n, ut.ctypes.data if len(ut) else None, st.ctypes.data if len(st) else None)
     with torch.cuda.device(dev):
-        nbytes = L.lib().dicow_orc_distance_ws_bytes(*tables, int(bool(want_assignment)))
-        if nbytes < 0:
-            raise L.DicowError(f"orc_counts: {L.lib().dicow_last_error().decode()}")
-        ws = ops.workspace(nbytes, dev)
+        ws, nbytes = ops.table_workspace("orc_counts", L.lib().dicow_orc_distance_ws_bytes, *tables, int(bool(want_assignment)), device=dev)
         L.call("dicow_orc_distance", ref_ids.data_ptr(), ref_ids.numel(), hyp_ids.data_ptr(), hyp_ids.numel(), L.ptr(ref_iv), L.ptr(hyp_iv),
                *tables, out.data_ptr(), L.ptr(asg), ws.data_ptr(), nbytes, L.stream())
     n_ref = [int(ut[r[0]:r[0] + r[1], 1].sum()) for r in pt]
