@@ -1,24 +1,22 @@
-"""Decoding side of the path: encoder once, KV-cached greedy decoder, STNO seek windows.
+"""Decoding side of the path: what the reference's evaluation drives through HF's generate.
 
-Mirrors, for the in-training evaluation the reference runs every ``eval_steps``:
   * ``stno_seek_windows``   reference DiCoWGenerationMixin.prepare_kwargs_for_generate (src/models/dicow/generation.py
                             :73-106): the STNO mask of each active sample's current 30 s window, padded as silence;
-  * ``GreedyDecoder``       the compute HF greedy search drives through the DiCoW model: the STNO-conditioned encoder runs
-                            ONCE per window, the cross-attention K/V of every decoder layer are projected ONCE, and each new
-                            token costs one decoder step against a per-layer self-attention KV cache; logits go through the
-                            SuppressTokens / SuppressTokensAtBegin processors the reference wires (generation.py:286-306),
-                            finished rows are padded, decoding stops when every row has produced eos.
-
-  * ``timestamp_rules``     WhisperTimeStampLogitsProcessorCustom (src/models/dicow/utils.py:5-14) as one kernel per step;
-  * ``repetition_rules``    transformers' RepetitionPenaltyLogitsProcessor + NoRepeatNGramLogitsProcessor (generation_config
-                            .repetition_penalty / .no_repeat_ngram_size) as one kernel per step, first in the chain as in HF;
-  * joint CTC / attention   ``ctc=dict(...)`` switches on ctc_decoding.CtcRescorer (decoding.py) after a log-softmax, as the
-                            reference wires it for greedy search (generation.py:249-268).
+  * ``timestamp_rules``, ``repetition_rules``   Whisper's timestamp processor and HF's two history processors, one kernel each;
+  * ``ProcessorChain``      the ONE place that orders a step's processors -- repetition rules, suppress lists, timestamp rules,
+                            joint CTC / attention term (ctc_decoding.CtcRescorer) -- for greedy and beam decoding alike;
+  * ``GreedyDecoder``       the STNO-conditioned encoder runs ONCE per window, the cross-attention K/V of every decoder layer are
+                            projected ONCE, and each new token costs one decoder step (``_step``, replayed from a hipGraph under
+                            ``use_graphs``) against a per-layer self-attention KV cache.  ``generate``: greedy search or sampling
+                            over one [B, P + max_new_tokens] token history; ``beam_search``: the reference's ``_beam_search`` on
+                            beam-indirect caches (``advance_ancestry``); ``generate_with_fallback``: Whisper's temperature
+                            ladder (``decode_with_fallback``); ``detect_language``: one decoder position;
+  * ``LongFormDecoder``     the seek loop over recordings longer than one window (``retrieve_segment``); its segments go back
+                            into window-relative tokens through ``fix_timestamps_from_segmentation``.
 
 Every matrix product, attention and LayerNorm is a C-ABI kernel call (the training step's kernels; single-row queries go
-through dicow_attn_fwd with Lq = 1, the <= 16-row products through the weight-streaming gemm_nt_skinny_kernel).  Not here:
-beam search, temperature fallback and the long-form seek loop of HF's generate -- host control flow around this step
-function.  No CPU fallback.
+through dicow_attn_fwd with Lq = 1, beam rows through dicow_attn_decode, the <= 16-row products through the weight-streaming
+gemm_nt_skinny_kernel); selection, processors and seek loops are host control flow around that step.  No CPU fallback.
 """
 from types import SimpleNamespace as NS
 
@@ -105,6 +103,53 @@ def advance_ancestry(anc, beam_idx, pos):
         anc[:, :pos] = anc[:, :pos].index_select(0, idx)             # (index_select copies before the write)
     anc[:, pos] = idx.to(anc.dtype)
     return anc
+
+
+def _eos_pad(cfg, eos_token_id=None, pad_token_id=None):
+    """(eos, pad): the model config's ids wherever the caller gave none."""
+    return (cfg.eos_token_id if eos_token_id is None else eos_token_id, cfg.pad_token_id if pad_token_id is None else pad_token_id)
+
+
+class ProcessorChain:
+    """One window's logits processors, in the order the reference runs them: HF's own history processors in front of
+    Whisper's (``repetition_rules``), SuppressTokens / SuppressTokensAtBegin (generation.py:286-306), the timestamp rules
+    (return_timestamps=True, generation.py:272-281), then the joint CTC / attention term (generation.py:249-268).
+    ``chain(ids, scores)`` processes one step's fp32 scores [rows, V] IN PLACE given the history ids [rows, cur] = prompt
+    (P tokens) + the tokens chosen so far, rows = batch x num_beams.  logprobs says what ``scores`` are: True -- already
+    log-probabilities (beam search: nothing more is normalised), False -- raw logits (greedy: the log-softmax sits in front of
+    the CTC term and runs only when that term is on)."""
+
+    def __init__(self, model, enc_out, prompt, eos, suppress_tokens, begin_suppress_tokens, timestamps, ctc, rep, num_beams, logprobs):
+        dev = enc_out.device
+        self.P, self.eos, self.timestamps, self.rep, self.logprobs = prompt.shape[1], eos, timestamps, rep, logprobs
+        self.sup = None if not suppress_tokens else torch.as_tensor(list(suppress_tokens), device=dev)
+        self.bsup = None if not begin_suppress_tokens else torch.as_tensor(list(begin_suppress_tokens), device=dev)
+        self.rescorer = None
+        if ctc is not None and ctc.get("weight", 0.0) > 0.0:
+            from .ctc_decoding import CtcRescorer
+            self.rescorer = CtcRescorer(model.get_enc_logits(enc_out), model.config.vocab_size, eos, prompt[0, 0].item(),
+                                        ctc["first_timestamp"], ctc.get("upper_cased", ()), ctc.get("prefix_len", self.P), ctc["weight"],
+                                        ctc.get("n_score", 500), num_beams=num_beams)
+            self.rows = torch.arange(prompt.shape[0] * num_beams, device=dev)
+
+    def __call__(self, ids, scores):
+        if self.rep is not None:
+            scores = repetition_rules(ids, scores, *self.rep)
+        if self.sup is not None:
+            scores[:, self.sup] = -float("inf")
+        if self.bsup is not None and ids.shape[1] == self.P:          # the first generated position
+            scores[:, self.bsup] = -float("inf")
+        if self.timestamps is not None:
+            scores = timestamp_rules(ids, scores, self.P, self.eos, self.timestamps["no_timestamps_token_id"],
+                                     self.timestamps.get("max_initial_timestamp_index"))
+        if self.rescorer is not None:
+            scores = self.rescorer(ids, scores if self.logprobs else torch.log_softmax(scores, dim=-1))
+        return scores
+
+    def advance(self, tokens, beam_idx=None):
+        """tokens [rows]: what each row continues with; beam_idx [rows]: the row it continues (None: itself)."""
+        if self.rescorer is not None:
+            self.rescorer.update_state(tokens, self.rows if beam_idx is None else beam_idx)
 
 
 def _rows3(t, B, H):
@@ -252,10 +297,9 @@ class GreedyDecoder:
                     timestamps=None, ctc=None, reorder_caches=False, repetition_penalty=None, no_repeat_ngram_size=None):
         """Beam search as the reference runs it (DiCoWGenerationMixin._beam_search, generation.py:815-1153, on transformers'
         vectorised beam helpers): per step the top 2K continuations over beams x vocabulary, the K best unfinished keep running,
-        finished ones compete for the K result slots with length-penalised scores; processors act on log-probabilities
-        (suppress lists, timestamp rules, joint CTC term without a second log-softmax, generation.py:249-268); KV caches and
-        the CTC states follow ``beam_idx``.  repetition_penalty / no_repeat_ngram_size: ``repetition_rules`` on the log-probabilities,
-        first in the chain (where HF's beam search applies its processors).  Returns (sequences [B, <= max_length], scores [B]) of the best hypothesis.
+        finished ones compete for the K result slots with length-penalised scores; the ``ProcessorChain`` acts on
+        log-probabilities (where HF's beam search applies its processors); KV caches and the CTC states follow ``beam_idx``.
+        Returns (sequences [B, <= max_length], scores [B]) of the best hypothesis.
 
         The caches follow their beams WITHOUT being copied: a window's cross-attention K/V exist once and are read by its K
         rows (ops.attn_decode, group=K); every row writes its self-attention key / value into its own slot and reads position j
@@ -265,8 +309,7 @@ class GreedyDecoder:
         reorder_caches=True: the former path (K/V repeated per beam, index_select copies of every cache per token, attn_fwd) --
         the A/B partner of the tests and tools/bench_decode.py, and what K > ops' MAX_GROUP falls back to; it cannot be graphed."""
         cfg, K = self.cfg, int(num_beams)
-        eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
-        pad = cfg.pad_token_id if pad_token_id is None else pad_token_id
+        eos, pad = _eos_pad(cfg, eos_token_id, pad_token_id)
         reorder_caches = bool(reorder_caches) or K > L.ATTN_DECODE_MAX_GROUP
         rep = repetition_options(repetition_penalty, no_repeat_ngram_size)
         if self.use_graphs and (reorder_caches or K == 1):           # (one beam: no indirect state; refused under graphs as before)
@@ -283,13 +326,8 @@ class GreedyDecoder:
         max_length = min(int(max_length), cfg.max_target_positions)
         if P < 1 or P >= max_length:
             raise ValueError(f"prompt length {P} leaves no room below max_length {max_length}")
-        sup = None if not suppress_tokens else torch.as_tensor(list(suppress_tokens), device=dev)
-        bsup = None if not begin_suppress_tokens else torch.as_tensor(list(begin_suppress_tokens), device=dev)
-        rescorer = None
-        if ctc is not None and ctc.get("weight", 0.0) > 0.0:
-            from .ctc_decoding import CtcRescorer
-            rescorer = CtcRescorer(self.model.get_enc_logits(st.enc_out), V, eos, prompt[0, 0].item(), ctc["first_timestamp"],
-                                   ctc.get("upper_cased", ()), ctc.get("prefix_len", P), ctc["weight"], ctc.get("n_score", 500), num_beams=K)
+        chain = ProcessorChain(self.model, st.enc_out, prompt, eos, suppress_tokens, begin_suppress_tokens, timestamps, ctc, rep,
+                               num_beams=K, logprobs=True)
         fill = pad if pad is not None else eos
         run_seq = torch.full((B, K, max_length), fill, dtype=torch.long, device=dev)
         run_seq[:, :, :P] = prompt[:, None, :]
@@ -314,17 +352,7 @@ class GreedyDecoder:
         cur = P
         while True:
             flat = run_seq[:, :, :cur].reshape(B * K, cur)
-            logp = torch.log_softmax(step(flat[:, -1].contiguous(), cur - 1, st).float(), dim=-1)
-            if rep is not None:
-                logp = repetition_rules(flat, logp, *rep)
-            if sup is not None:
-                logp[:, sup] = -float("inf")
-            if bsup is not None and cur == P:
-                logp[:, bsup] = -float("inf")
-            if timestamps is not None:
-                logp = timestamp_rules(flat, logp, P, eos, timestamps["no_timestamps_token_id"], timestamps.get("max_initial_timestamp_index"))
-            if rescorer is not None:
-                logp = rescorer(flat, logp)
+            logp = chain(flat, torch.log_softmax(step(flat[:, -1].contiguous(), cur - 1, st).float(), dim=-1))
             acc = (logp.view(B, K, V) + run_sc[:, :, None]).reshape(B, K * V)
             tk_lp, tk = torch.topk(acc, k=2 * K)
             src = tk // V
@@ -350,8 +378,7 @@ class GreedyDecoder:
                 for c in st.layers:                                  # the caches follow their beams
                     c.k[:, :cur].copy_(c.k[:, :cur].index_select(0, beam_idx))
                     c.v[:, :cur].copy_(c.v[:, :cur].index_select(0, beam_idx))
-            if rescorer is not None:
-                rescorer.update_state(run_seq.reshape(B * K, -1)[:, cur], beam_idx)
+            chain.advance(run_seq.reshape(B * K, -1)[:, cur], beam_idx)
             cur += 1
             hyp_len = (max_length - P) if (early_stopping == "never" and length_penalty > 0.0) else (cur - P)
             best = run_sc[:, :1] / float(hyp_len ** length_penalty)
@@ -369,60 +396,39 @@ class GreedyDecoder:
                  timestamps=None, temperature=0.0, generator=None, no_speech_token_id=None, repetition_penalty=None,
                  no_repeat_ngram_size=None):
         """decoder_input_ids int64 [B, P]: the forced prefix (start token, language / task / timestamp tokens).
-        ctc: dict(weight=..., first_timestamp=..., upper_cased=[(lo, up), ...], prefix_len=..., n_score=500) switches on the
-        joint CTC / attention scoring of generation.py:249-268 (log-softmax, then ctc_decoding.CtcRescorer on the model's CTC head).
-        timestamps: dict(no_timestamps_token_id=..., max_initial_timestamp_index=...) applies Whisper's timestamp rules
-        (return_timestamps=True in the reference, generation.py:272-281), after the suppress lists and before the CTC term.
-        repetition_penalty / no_repeat_ngram_size: ``repetition_rules`` on the step's raw logits, before the suppress lists (HF's
-        order: its own processors run in front of Whisper's).
+        The step's raw logits go through the ``ProcessorChain``: repetition_penalty / no_repeat_ngram_size, the suppress lists,
+        timestamps: dict(no_timestamps_token_id=..., max_initial_timestamp_index=...) for Whisper's timestamp rules, and
+        ctc: dict(weight=..., first_timestamp=..., upper_cased=[(lo, up), ...], prefix_len=..., n_score=500) for the joint
+        CTC / attention scoring (log-softmax, then ctc_decoding.CtcRescorer on the model's CTC head).
         temperature > 0: multinomial sampling from softmax(processed scores / temperature) (HF's sample mode, what Whisper's
         temperature fallback decodes with; `generator` makes it reproducible); the returned scores are then the temperature-scaled
         ones, as HF's are.  no_speech_token_id: also keep softmax(logits of the position after the start token)[that id] per row
         in ``self.no_speech_prob`` (HF WhisperNoSpeechDetection).
         Returns sequences [B, P + n] (and the processed fp32 scores [n, B, V] of the generated positions)."""
         cfg = self.cfg
-        eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
-        pad = cfg.pad_token_id if pad_token_id is None else pad_token_id
+        eos, pad = _eos_pad(cfg, eos_token_id, pad_token_id)
         st = self.encode(input_features, stno_mask, enrollments)
         dev = st.enc_out.device
         ids = decoder_input_ids.to(dev)
         B, P = ids.shape
         if P < 1 or P + max_new_tokens > cfg.max_target_positions:
             raise ValueError(f"prompt {P} + max_new_tokens {max_new_tokens} exceeds max_target_positions {cfg.max_target_positions}")
-        sup = None if not suppress_tokens else torch.as_tensor(list(suppress_tokens), device=dev)
-        bsup = None if not begin_suppress_tokens else torch.as_tensor(list(begin_suppress_tokens), device=dev)
-        rescorer = None
-        if ctc is not None and ctc.get("weight", 0.0) > 0.0:
-            from .ctc_decoding import CtcRescorer
-            enc_logits = self.model.get_enc_logits(st.enc_out)
-            rescorer = CtcRescorer(enc_logits, cfg.vocab_size, eos, ids[0, 0].item(), ctc["first_timestamp"], ctc.get("upper_cased", ()),
-                                   ctc.get("prefix_len", P), ctc["weight"], ctc.get("n_score", 500))
-            rows = torch.arange(B, device=dev)
-        rep = repetition_options(repetition_penalty, no_repeat_ngram_size)
+        chain = ProcessorChain(self.model, st.enc_out, ids, eos, suppress_tokens, begin_suppress_tokens, timestamps, ctc,
+                               repetition_options(repetition_penalty, no_repeat_ngram_size), num_beams=1, logprobs=False)
         step = self._step_graphed if self.use_graphs else self._step
         self.no_speech_prob = None
-        for t in range(P - 1):                                       # prefill the caches with the prefix
-            lg = step(ids[:, t], t, st)
-            if t == 0 and no_speech_token_id is not None:
-                self.no_speech_prob = torch.softmax(lg.float(), dim=-1)[:, no_speech_token_id].clone()
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
-        seq, scores = [ids], []
-        cur = ids[:, P - 1]
-        for n in range(max_new_tokens):
-            logits = step(cur, P - 1 + n, st)
-            if n == 0 and P == 1 and no_speech_token_id is not None:
+        hist = torch.empty(B, P + max_new_tokens, dtype=torch.long, device=dev)    # the token history: position t sees hist[:, :t + 1]
+        hist[:, :P] = ids
+        scores, end, cur = [], P, ids[:, 0]
+        for t in range(P - 1 + max_new_tokens):
+            logits = step(cur, t, st)
+            if t == 0 and no_speech_token_id is not None:            # the position after the start token, before any processor
                 self.no_speech_prob = torch.softmax(logits.float(), dim=-1)[:, no_speech_token_id].clone()
-            if rep is not None:
-                logits = repetition_rules(torch.cat(seq, dim=1), logits, *rep)
-            if sup is not None:
-                logits[:, sup] = -float("inf")
-            if bsup is not None and n == 0:
-                logits[:, bsup] = -float("inf")
-            if timestamps is not None:
-                logits = timestamp_rules(torch.cat(seq, dim=1), logits, P, eos, timestamps["no_timestamps_token_id"],
-                                         timestamps.get("max_initial_timestamp_index"))
-            if rescorer is not None:
-                logits = rescorer(torch.cat(seq, dim=1), torch.log_softmax(logits, dim=-1))
+            if t < P - 1:                                            # inside the forced prefix: the step only fills the caches
+                cur = ids[:, t + 1]
+                continue
+            logits = chain(hist[:, :t + 1], logits)
             if temperature and temperature > 0.0:
                 logits = logits / temperature
             if return_scores:
@@ -432,14 +438,13 @@ class GreedyDecoder:
             else:
                 nxt = logits.argmax(-1)
             nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
-            if rescorer is not None:
-                rescorer.update_state(nxt, rows)
-            seq.append(nxt[:, None])
+            chain.advance(nxt)
+            hist[:, t + 1] = cur = nxt
+            end = t + 2
             unfinished = unfinished & (nxt != eos)
-            cur = nxt
             if not bool(unfinished.any()):
                 break
-        out = torch.cat(seq, dim=1)
+        out = hist[:, :end].clone()                                  # contiguous, and its own storage
         return (out, torch.stack(scores)) if return_scores else out
 
     @torch.no_grad()
@@ -452,11 +457,7 @@ class GreedyDecoder:
         window that is unlikely AND looks like silence (no_speech_prob) is skipped instead.  gen_kw: generate()'s processor
         arguments (eos / pad ids, suppress lists, timestamps, ctc, repetition_penalty, no_repeat_ngram_size).
         Returns (token lists of the generated positions without the eos, should_skip flags, temperature index per window)."""
-        cfg = self.cfg
-        eos = gen_kw.get("eos_token_id", None)
-        eos = cfg.eos_token_id if eos is None else eos
-        pad = gen_kw.get("pad_token_id", None)
-        pad = cfg.pad_token_id if pad is None else pad
+        eos, pad = _eos_pad(self.cfg, gen_kw.get("eos_token_id"), gen_kw.get("pad_token_id"))
         B, P = decoder_input_ids.shape
         if no_speech_threshold is not None and no_speech_token_id is None:
             raise ValueError("no_speech_threshold needs no_speech_token_id")
@@ -470,7 +471,7 @@ class GreedyDecoder:
             toks = seqs[:, P:].tolist()
             return toks, [scores[:, i] for i in range(len(rows))], self.no_speech_prob
 
-        return decode_with_fallback(decode, B, tuple(temperatures), cfg.vocab_size, pad, eos, compression_ratio_threshold,
+        return decode_with_fallback(decode, B, tuple(temperatures), self.cfg.vocab_size, pad, eos, compression_ratio_threshold,
                                     logprob_threshold, no_speech_threshold, skip_by_row=skip_by_row)
 
 
@@ -702,8 +703,7 @@ class LongFormDecoder:
         former copying path).
         Returns per recording a list of segments dict(start, end, tokens) in seconds / token ids."""
         cfg = self.cfg
-        eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
-        pad = cfg.pad_token_id if pad_token_id is None else pad_token_id
+        eos, pad = _eos_pad(cfg, eos_token_id, pad_token_id)
         ts0 = no_timestamps_token_id + 1
         W = 2 * cfg.max_source_positions                           # feature frames per window
         B, M, _ = input_features.shape
@@ -713,6 +713,19 @@ class LongFormDecoder:
         prompt = decoder_input_ids if decoder_input_ids.shape[0] == B else decoder_input_ids.expand(B, -1)
         P = prompt.shape[1]
         n_new = (cfg.max_target_positions - P) if max_new_tokens is None else max_new_tokens
+        # the decoder's keywords, the same for every window (only ``enrollments`` is cut to the active rows inside the loop)
+        ts = dict(no_timestamps_token_id=no_timestamps_token_id, max_initial_timestamp_index=gen_kw.get("max_initial_timestamp_index", 50))
+        kw = dict(eos_token_id=eos, pad_token_id=pad, timestamps=ts,
+                  **{k: gen_kw.get(k) for k in ("suppress_tokens", "begin_suppress_tokens", "ctc", "repetition_penalty", "no_repeat_ngram_size")})
+        ladder = gen_kw.get("temperatures") is not None and self.num_beams == 1
+        if ladder:
+            # temperature fallback (reference generation.py:567-611): per-window ladder, silent windows skipped (skip_by_row=True
+            # keeps a silent window's flag with ITS recording; default = transformers' position in the sub-batch, see decode_with_fallback)
+            kw.update({k: gen_kw[k] for k in ("temperatures", "compression_ratio_threshold", "logprob_threshold", "no_speech_threshold",
+                                              "no_speech_token_id", "generator", "skip_by_row") if k in gen_kw})
+        elif self.num_beams > 1:
+            kw.update(length_penalty=gen_kw.get("length_penalty", 1.0), early_stopping=gen_kw.get("early_stopping", False),
+                      reorder_caches=gen_kw.get("reorder_caches", False))
         while True:
             active = [b for b in range(B) if seek[b] < max_frames[b]]
             if not active:
@@ -723,29 +736,14 @@ class LongFormDecoder:
                 feats[i, :, :left[i]] = input_features[b, :, seek[b]:seek[b] + left[i]]
             stno = stno_seek_windows(stno_mask, seek, max_frames, active, num_frames=cfg.max_source_positions)
             enr = None if enrollments is None else {k: v[active] for k, v in enrollments.items()}
-            kw = dict(eos_token_id=eos, pad_token_id=pad, enrollments=enr,
-                      timestamps=dict(no_timestamps_token_id=no_timestamps_token_id,
-                                      max_initial_timestamp_index=gen_kw.get("max_initial_timestamp_index", 50)),
-                      suppress_tokens=gen_kw.get("suppress_tokens"), begin_suppress_tokens=gen_kw.get("begin_suppress_tokens"),
-                      ctc=gen_kw.get("ctc"), repetition_penalty=gen_kw.get("repetition_penalty"),
-                      no_repeat_ngram_size=gen_kw.get("no_repeat_ngram_size"))
             skip = [False] * len(active)
-            if gen_kw.get("temperatures") is not None and self.num_beams == 1:
-                # temperature fallback (reference generation.py:567-611): per-window ladder, silent windows skipped
-                # (skip_by_row=True: keep a silent window's skip flag with ITS recording instead of transformers' position in
-                # the fallback sub-batch -- see decode_with_fallback; default = the reference's behaviour)
-                fb = {k: gen_kw[k] for k in ("compression_ratio_threshold", "logprob_threshold", "no_speech_threshold",
-                                             "no_speech_token_id", "generator", "skip_by_row") if k in gen_kw}
-                tok_lists, skip, _ = self.decoder.generate_with_fallback(feats, stno, prompt[active], n_new,
-                                                                         temperatures=gen_kw["temperatures"], **fb, **kw)
-            elif self.num_beams > 1:
-                seqs, _ = self.decoder.beam_search(feats, stno, prompt[active], P + n_new, self.num_beams,
-                                                   length_penalty=gen_kw.get("length_penalty", 1.0),
-                                                   early_stopping=gen_kw.get("early_stopping", False),
-                                                   reorder_caches=gen_kw.get("reorder_caches", False), **kw)
-                tok_lists = [seqs[i, P:].tolist() for i in range(len(active))]
+            if ladder:
+                tok_lists, skip, _ = self.decoder.generate_with_fallback(feats, stno, prompt[active], n_new, enrollments=enr, **kw)
             else:
-                seqs = self.decoder.generate(feats, stno, prompt[active], n_new, **kw)
+                if self.num_beams > 1:
+                    seqs, _ = self.decoder.beam_search(feats, stno, prompt[active], P + n_new, self.num_beams, enrollments=enr, **kw)
+                else:
+                    seqs = self.decoder.generate(feats, stno, prompt[active], n_new, enrollments=enr, **kw)
                 tok_lists = [seqs[i, P:].tolist() for i in range(len(active))]
             for i, b in enumerate(active):
                 if skip[i]:                                          # HF: a skipped (silent) window only moves the seek pointer

@@ -777,7 +777,7 @@ class DiCoWForConditionalGeneration(_ModelBase):
         begin_suppress_tokens, return_timestamps, no_timestamps_token_id, max_initial_timestamp_index, ctc_weight,
         repetition_penalty, no_repeat_ngram_size, ...).
         The prompt is ``decoder_input_ids`` or [decoder_start_token_id] + the tokenizer's prefix tokens."""
-        from .generation import GreedyDecoder
+        from .generation import repetition_options
         gc = generation_config if generation_config is not None else self.generation_config
         # (explicit keyword arguments win over the generation config, as in HF's generate)
         # -- except `temperature`, which HF's WhisperGenerationMixin.generate (the method the reference delegates to) takes from
@@ -795,12 +795,17 @@ class DiCoWForConditionalGeneration(_ModelBase):
         self.stno_mask = stno_mask                            # reference generate() keeps it for detect_language (generation.py:556)
         cfg = self.config
         ts_on = return_timestamps if return_timestamps is not None else get("return_timestamps", False)
-        one_window = input_features.shape[-1] == 2 * cfg.max_source_positions
+        n_frames, window = input_features.shape[-1], 2 * cfg.max_source_positions
+        # HF's generate -- which the reference's calls (generation.py:558) -- runs its seek loop on EVERY input: a single window
+        # that ends in an open timestamp gets a second pass over its tail, and the return value is the segment-derived matrix of
+        # _fix_timestamps_from_segmentation.  With timestamps on and a real tokenizer set (the fix-up needs its ids) a
+        # one-window input therefore takes the same path as a long recording; all of its frames count as valid by default.
+        one_window_seek = n_frames == window and ts_on and hasattr(self.tokenizer, "get_vocab")
+        takes_seek_loop = one_window_seek or n_frames > window
         # Sampling / fallback arguments that are not honoured on a path raise instead of being ignored (cf. _refuse_unsupported):
         # HF samples at a scalar temperature > 0 and runs generate_with_fallback inside its seek loop on every input.
         temps = get("temperature")
         ladder = isinstance(temps, (tuple, list))
-        takes_seek_loop = (one_window and ts_on and hasattr(self.tokenizer, "get_vocab")) or input_features.shape[-1] > 2 * cfg.max_source_positions
         if temps is not None and not ladder and float(temps) > 0.0:
             raise NotImplementedError("generate(temperature=t > 0): plain sampling is not implemented; pass a tuple (0.0, 0.2, ...) for "
                                       "the temperature-fallback ladder (GreedyDecoder.generate(temperature=...) samples one window)")
@@ -812,70 +817,64 @@ class DiCoWForConditionalGeneration(_ModelBase):
         if get("no_speech_threshold") is not None and get("logprob_threshold") is None and ladder:
             raise ValueError("no_speech_threshold only takes effect together with logprob_threshold (a window is skipped when it is "
                              "unlikely AND silent)")
-        # HF's generate -- which the reference's calls (generation.py:558) -- runs its seek loop on EVERY input: a single window
-        # that ends in an open timestamp gets a second pass over its tail, and the return value is the segment-derived matrix of
-        # _fix_timestamps_from_segmentation.  With timestamps on and a real tokenizer set (the fix-up needs its ids) a
-        # one-window input therefore takes the same path as a long recording; all of its frames count as valid by default.
         # HF's own two history processors (generation.repetition_rules), first in the chain on every path; validated here so that a
         # bad value raises before any window is decoded
-        from .generation import repetition_options
         rep_kw = dict(repetition_penalty=get("repetition_penalty"), no_repeat_ngram_size=get("no_repeat_ngram_size"))
         repetition_options(**rep_kw)
-        if one_window and ts_on and hasattr(self.tokenizer, "get_vocab"):
-            if attention_mask is None:
-                attention_mask = torch.ones(input_features.shape[0], input_features.shape[-1], dtype=torch.long, device=input_features.device)
+        if takes_seek_loop:
+            if one_window_seek and attention_mask is None:
+                attention_mask = torch.ones(input_features.shape[0], n_frames, dtype=torch.long, device=input_features.device)
             return self._generate_long_form(input_features, stno_mask, attention_mask, decoder_input_ids, max_new_tokens, get, beams,
                                             enrollments, gc, rep_kw)
-        if input_features.shape[-1] > 2 * cfg.max_source_positions:
-            return self._generate_long_form(input_features, stno_mask, attention_mask, decoder_input_ids, max_new_tokens, get, beams,
-                                            enrollments, gc, rep_kw)
-        if input_features.shape[-1] != 2 * cfg.max_source_positions:
+        if n_frames != window:
             raise ValueError("input_features shorter than one window: pad the features to 2 * max_source_positions frames")
-        B = input_features.shape[0]
-        if decoder_input_ids is None and get("lang_to_id") is not None:
-            decoder_input_ids = self.retrieve_init_tokens(input_features, stno_mask, gc, enrollments, return_timestamps)
-        elif decoder_input_ids is None:
-            prefix = list(getattr(self.tokenizer, "prefix_tokens", [])) if self.tokenizer is not None else []
-            start = get("decoder_start_token_id", cfg.decoder_start_token_id)
-            prompt = prefix if (prefix and prefix[0] == start) else [start] + prefix
-            decoder_input_ids = torch.tensor([prompt] * B, dtype=torch.long)
+        if decoder_input_ids is None:
+            decoder_input_ids = self._default_prompt(input_features, stno_mask, gc, get, enrollments, return_timestamps,
+                                                     rows=input_features.shape[0])
         P = decoder_input_ids.shape[1]
         if max_new_tokens is None:
             limit = max_length if max_length is not None else get("max_length", cfg.max_target_positions)
             max_new_tokens = min(limit, cfg.max_target_positions) - P
-        ts = return_timestamps if return_timestamps is not None else get("return_timestamps", False)
         timestamps = None
-        if ts:
+        if ts_on:
             timestamps = dict(no_timestamps_token_id=get("no_timestamps_token_id"),
                               max_initial_timestamp_index=get("max_initial_timestamp_index"))
-        ctc = None
-        if (get("ctc_weight", 0.0) or 0.0) > 0.0:
-            tok = self.tokenizer
-            ctc = dict(weight=get("ctc_weight"), first_timestamp=tok.get_vocab()["<|0.00|>"],
-                       upper_cased=list(getattr(tok, "upper_cased_tokens", {}).items()), prefix_len=len(tok.prefix_tokens))
+        kw = dict(eos_token_id=get("eos_token_id", cfg.eos_token_id), pad_token_id=get("pad_token_id", cfg.pad_token_id),
+                  suppress_tokens=get("suppress_tokens"), begin_suppress_tokens=get("begin_suppress_tokens"),
+                  enrollments=enrollments, timestamps=timestamps, ctc=self._ctc_options(get), **rep_kw)
+        dec = self._decoder_for(use_graphs)
+        if beams > 1:                                        # reference: generation_num_beams 5 in configs/decode/*_beam_joint.yaml
+            return dec.beam_search(input_features, stno_mask, decoder_input_ids, P + max_new_tokens, beams,
+                                   length_penalty=get("length_penalty", 1.0), early_stopping=get("early_stopping", False), **kw)[0]
+        return dec.generate(input_features, stno_mask, decoder_input_ids, max_new_tokens, **kw)
+
+    def _decoder_for(self, use_graphs=False):
+        """The model's decoder; under use_graphs the one that replays each decoder position from its hipGraph (evaluation: fixed
+        weights; beam search on the beam-indirect caches is captured too).  Both are kept for the model's lifetime."""
+        from .generation import GreedyDecoder
         if not hasattr(self, "_decoder"):
             self._decoder = GreedyDecoder(self)
-        if beams > 1:                                        # reference: generation_num_beams 5 in configs/decode/*_beam_joint.yaml
-            dec = self._decoder
-            if use_graphs:                                   # (beam search on the beam-indirect caches: its step is captured too)
-                if not hasattr(self, "_decoder_graphed"):
-                    self._decoder_graphed = GreedyDecoder(self, use_graphs=True)
-                dec = self._decoder_graphed
-            seq, _ = dec.beam_search(input_features, stno_mask, decoder_input_ids, P + max_new_tokens, beams,
-                                     eos_token_id=get("eos_token_id", cfg.eos_token_id), pad_token_id=get("pad_token_id", cfg.pad_token_id),
-                                     length_penalty=get("length_penalty", 1.0), early_stopping=get("early_stopping", False),
-                                     suppress_tokens=get("suppress_tokens"), begin_suppress_tokens=get("begin_suppress_tokens"),
-                                     enrollments=enrollments, timestamps=timestamps, ctc=ctc, **rep_kw)
-            return seq
-        dec = self._decoder
-        if use_graphs:                                       # hipGraph replay of each decoder position (evaluation: fixed weights)
-            if not hasattr(self, "_decoder_graphed"):
-                self._decoder_graphed = GreedyDecoder(self, use_graphs=True)
-            dec = self._decoder_graphed
-        return dec.generate(input_features, stno_mask, decoder_input_ids, max_new_tokens,
-                                      eos_token_id=get("eos_token_id", cfg.eos_token_id), pad_token_id=get("pad_token_id", cfg.pad_token_id),
-                                      suppress_tokens=get("suppress_tokens"), begin_suppress_tokens=get("begin_suppress_tokens"),
-                                      enrollments=enrollments, ctc=ctc, timestamps=timestamps, **rep_kw)
+        if use_graphs and not hasattr(self, "_decoder_graphed"):
+            self._decoder_graphed = GreedyDecoder(self, use_graphs=True)
+        return self._decoder_graphed if use_graphs else self._decoder
+
+    def _ctc_options(self, get):
+        """The decoders' ``ctc`` dict (joint CTC / attention scoring) from ``ctc_weight`` and the tokenizer, or None when off."""
+        if not (get("ctc_weight", 0.0) or 0.0) > 0.0:
+            return None
+        tok = self.tokenizer
+        return dict(weight=get("ctc_weight"), first_timestamp=tok.get_vocab()["<|0.00|>"],
+                    upper_cased=list(getattr(tok, "upper_cased_tokens", {}).items()), prefix_len=len(tok.prefix_tokens))
+
+    def _default_prompt(self, input_features, stno_mask, gc, get, enrollments, return_timestamps, rows, drop=None):
+        """The prompt of a call without ``decoder_input_ids``: ``retrieve_init_tokens`` when the generation config knows the
+        language tokens, else [decoder_start_token_id] + the tokenizer's prefix tokens on ``rows`` rows.  drop: a token id left
+        out of that prefix (the long form's <|notimestamps|>: timestamps are predicted there)."""
+        if get("lang_to_id") is not None:
+            return self.retrieve_init_tokens(input_features, stno_mask, gc, enrollments, return_timestamps)
+        prefix = [t for t in getattr(self.tokenizer, "prefix_tokens", []) if t != drop] if self.tokenizer is not None else []
+        start = get("decoder_start_token_id", self.config.decoder_start_token_id)
+        return torch.tensor([prefix if (prefix and prefix[0] == start) else [start] + prefix] * rows, dtype=torch.long)
 
     def retrieve_init_tokens(self, input_features, stno_mask, generation_config, enrollments=None, return_timestamps=None):
         """The forced prompt per row the way the reference's evaluation gets it (DiCoWGenerationMixin._retrieve_init_tokens,
@@ -939,16 +938,9 @@ class DiCoWForConditionalGeneration(_ModelBase):
         vocab = tok.get_vocab()
         first_ts = vocab["<|0.00|>"]
         no_ts = get("no_timestamps_token_id", first_ts - 1)
-        if decoder_input_ids is None and get("lang_to_id") is not None:               # language from the first window
-            decoder_input_ids = self.retrieve_init_tokens(input_features, stno_mask, gc, enrollments, return_timestamps=True)
-        elif decoder_input_ids is None:
-            prefix = [t for t in getattr(tok, "prefix_tokens", []) if t != no_ts]          # timestamps are predicted
-            start = get("decoder_start_token_id", cfg.decoder_start_token_id)
-            decoder_input_ids = torch.tensor([prefix if (prefix and prefix[0] == start) else [start] + prefix], dtype=torch.long)
-        ctc = None
-        if (get("ctc_weight", 0.0) or 0.0) > 0.0:
-            ctc = dict(weight=get("ctc_weight"), first_timestamp=first_ts,
-                       upper_cased=list(getattr(tok, "upper_cased_tokens", {}).items()), prefix_len=len(tok.prefix_tokens))
+        if decoder_input_ids is None:                  # (language from the first window; one row: transcribe repeats it)
+            decoder_input_ids = self._default_prompt(input_features, stno_mask, gc, get, enrollments, True, rows=1, drop=no_ts)
+        ctc = self._ctc_options(get)
         eos = get("eos_token_id", cfg.eos_token_id)
         dec = LongFormDecoder(self, beams)
         fb = {}
@@ -973,16 +965,13 @@ class DiCoWForConditionalGeneration(_ModelBase):
                         num_segment_frames=None, lang_token_ids=None):
         """Language id per row from one decoder position (reference generation.py:151-221).  ``stno_mask`` defaults to the one
         stored by the last generate() call, as in the reference; language tokens come from ``generation_config.lang_to_id``."""
-        from .generation import GreedyDecoder
         gc = generation_config if generation_config is not None else self.generation_config
         if lang_token_ids is None:
             lang_token_ids = list(getattr(gc, "lang_to_id").values())
         if stno_mask is None:
             stno_mask = self.stno_mask
-        if not hasattr(self, "_decoder"):
-            self._decoder = GreedyDecoder(self)
         start = getattr(gc, "decoder_start_token_id", None) if gc is not None else None
-        return self._decoder.detect_language(input_features, stno_mask, lang_token_ids, start, enrollments)
+        return self._decoder_for().detect_language(input_features, stno_mask, lang_token_ids, start, enrollments)
 
     def post_init(self):
         """The reference's container calls it after ``from_pretrained`` (containers.py:52).  Nothing is re-initialised here (every module
