@@ -902,6 +902,40 @@ int dicow_whisper_timestamp_rules(float* scores, int64_t ld, int B, int V, const
 int dicow_repetition_rules(float* scores, int64_t ld, int rows, int V, const int64_t* input_ids, int64_t ids_stride, int L,
                            float penalty, int ngram, void* stream);
 
+/* Sequence bias and banned phrases on next-token scores, in place (ABI 7, additive): transformers' SequenceBiasLogitsProcessor, and
+ * with biases of -inf its NoBadWordsLogitsProcessor -- what HF's generate builds from generation_config.sequence_bias /
+ * .bad_words_ids (hotwords; forbidden phrases).
+ * scores fp32 [rows, ld >= V]; row r's history is the L >= 1 int64 entries at input_ids + r * ids_stride (ids_stride >= L).
+ * table: ONE device int32 array, built once per window by the caller (generation.sequence_bias_table), of
+ *     seq_off [n_seq + 1] | grp_off [n_groups + 1] | bias [n_seq] (fp32 bits) | tok [n_tokens]
+ *   sequence s is tok[seq_off[s] .. seq_off[s + 1]), 1 .. max_len tokens, every token in [0, V); its bias is finite or -inf (+inf and
+ *   NaN are refused by the host wrapper: transformers would turn -inf + inf into NaN); the sequences stand sorted (stably) by their last
+ *   token, group g = sequences grp_off[g] .. grp_off[g + 1) = all sequences of one last token, its single-token sequence (at most one)
+ *   first, the others in the caller's (dict) order; max_group = the longest group.
+ * Definition.  Sequence s of m tokens MATCHES row r if m == 1 (whatever the history: transformers' length-1 bias), or if m <= L and the
+ * last m - 1 history entries equal tok[0 .. m - 1) of s, compared by value as int64 (a history id outside [0, V) never matches); a
+ * sequence longer than the history is ignored.  For every group, v its last token: b = +0.0f; for each matching sequence in table order
+ * b = b + bias_s (one fp32 rounding per add); if at least one matched, scores[r, v] = scores[r, v] + b.  Nothing else is written:
+ * columns >= V, rows >= rows and every score whose token heads no matching sequence keep their bits -- so an untouched -0.0 stays -0.0,
+ * where transformers' `scores + bias` over the whole row returns +0.0 (the one difference in bits; as numbers the two are equal).
+ * One writer per score element, no atomics, no host table, no workspace: a row's result depends on that row's history and the table
+ * alone and is bit-identical from run to run and under every plan.  One launch, capturable; with n_seq == 0 nothing is launched (table
+ * may be NULL).
+ * plan: 0 = the library's choice (WAVE when max_group >= 64, else LANE), DICOW_SEQ_BIAS_LANE = a lane per group,
+ * DICOW_SEQ_BIAS_WAVE = a wave per group (matches balloted, added in lane order).
+ * Refused before anything is launched (-1, dicow_last_error() names the limit): L > DICOW_SEQ_BIAS_MAX_L, max_len >
+ * DICOW_SEQ_BIAS_MAX_LEN, n_seq > DICOW_SEQ_BIAS_MAX_SEQ, an unknown plan, counts that contradict each other.  The table's CONTENT is
+ * read on the device only: an entry that breaks the layout (a range outside the table, a token outside [0, V)) matches or writes
+ * nothing. */
+#define DICOW_SEQ_BIAS_MAX_L 8192
+#define DICOW_SEQ_BIAS_MAX_LEN 32
+#define DICOW_SEQ_BIAS_MAX_SEQ 65536
+#define DICOW_SEQ_BIAS_PLANS 2
+#define DICOW_SEQ_BIAS_LANE 1
+#define DICOW_SEQ_BIAS_WAVE 2
+int dicow_sequence_bias(float* scores, int64_t ld, int rows, int V, const int64_t* input_ids, int64_t ids_stride, int L,
+                        const int* table, int n_seq, int n_groups, int n_tokens, int max_len, int max_group, int plan, void* stream);
+
 /* Greedy CTC decoding (ABI 7, additive): ctc_greedy_decode of the reference (src/utils/decoding.py:6-12: torch.argmax, then a Python
  * itertools.groupby over every row of the device tensor), the preprocess_logits_for_metrics of CTC pre-training (src/pretrain_encoder.py:82-86).
  * logits fp32 / bf16 (in_bf16): frame t of batch row b starts at element b * batch_stride + t * ld; unit stride over the V1 <= ld classes.  The

@@ -101,6 +101,9 @@ BOOT_MAX_N, BOOT_MAX_C, BOOT_MAX_R, BOOT_LDS_BYTES, BOOT_PLANS = 1 << 24, 32, (1
 BOOT_LANE_LDS, BOOT_WAVE_LDS, BOOT_WAVE_L2 = 1, 2, 3
 BOOT_RESAMPLE, BOOT_SWAP = 0, 1
 
+# DICOW_SEQ_BIAS_*: dicow_sequence_bias's longest history, longest sequence, most sequences, and its plans
+SEQ_BIAS_MAX_L, SEQ_BIAS_MAX_LEN, SEQ_BIAS_MAX_SEQ, SEQ_BIAS_PLANS, SEQ_BIAS_LANE, SEQ_BIAS_WAVE = 8192, 32, 65536, 2, 1, 2
+
 LORA_MAX_R, LORA_MAX_SEG = 192, 24
 LORA_BLOCK, LORA_OUT_F32, LORA_GELU, LORA_MUL_AUX = 1, 2, 4, 8
 
@@ -217,6 +220,7 @@ _SIGS = {
     "dicow_ctc_prefix_score": [C.POINTER(CtcPrefixArgs), c_vp],
     "dicow_whisper_timestamp_rules": [c_vp, c_i64, c_i, c_i, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
     "dicow_repetition_rules": [c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_i, c_f, c_i, c_vp],
+    "dicow_sequence_bias": [c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_i, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
     "dicow_ctc_greedy_decode": [c_vp, c_i, c_i64, c_i64, c_i, c_i, c_i, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp],
     "dicow_ctc_forced_align": [c_vp, c_i, c_i, c_i, c_i, c_i64, c_vp, c_vp, c_i, c_vp, c_i, c_vp, c_i64, c_vp, c_i, c_vp, c_i, c_vp, c_vp, c_vp,
                                c_i, c_vp, c_i64, c_vp],

@@ -3,8 +3,11 @@
   * ``stno_seek_windows``   reference DiCoWGenerationMixin.prepare_kwargs_for_generate (src/models/dicow/generation.py
                             :73-106): the STNO mask of each active sample's current 30 s window, padded as silence;
   * ``timestamp_rules``, ``repetition_rules``   Whisper's timestamp processor and HF's two history processors, one kernel each;
-  * ``ProcessorChain``      the ONE place that orders a step's processors -- repetition rules, suppress lists, timestamp rules,
-                            joint CTC / attention term (ctc_decoding.CtcRescorer) -- for greedy and beam decoding alike;
+  * ``sequence_bias_rules``  HF's sequence_bias / bad_words_ids (hotwords, banned phrases): one kernel over a device table
+                            (``sequence_bias_options``, ``sequence_bias_table``; ``phrase_sequences`` turns phrases into ids);
+  * ``ProcessorChain``      the ONE place that orders a step's processors -- sequence bias, repetition rules, banned phrases,
+                            suppress lists, timestamp rules, joint CTC / attention term (ctc_decoding.CtcRescorer) -- for greedy
+                            and beam decoding alike;
   * ``GreedyDecoder``       the STNO-conditioned encoder runs ONCE per window, the cross-attention K/V of every decoder layer are
                             projected ONCE, and each new token costs one decoder step (``_step``, replayed from a hipGraph under
                             ``use_graphs``) against a per-layer self-attention KV cache.  ``generate``: greedy search or sampling
@@ -91,6 +94,144 @@ def repetition_rules(input_ids, scores, repetition_penalty=None, no_repeat_ngram
     return scores
 
 
+def _is_token(t):
+    import numpy as np
+    return isinstance(t, (int, np.integer))
+
+
+def sequence_bias_options(sequence_bias=None, bad_words_ids=None, eos_token_id=None, vocab_size=None):
+    """Validation of transformers' SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor arguments, with their error texts:
+    ``sequence_bias`` a dict {tuple of ids: float} or a list of [[ids], float]; ``bad_words_ids`` a list of lists of ids, of which
+    single-token entries equal to an eos id are dropped; a token >= vocab_size (when given) raises transformers' vocabulary error.
+    The project's own rule on top: a bias must be finite or -inf (+inf and NaN raise; transformers would compute NaN scores from
+    -inf + inf).  Returns None when both are off (None), else a pair (bias, banned), each None or (sequences, biases): tuples of ids
+    in the caller's order and one float per tuple (-inf for every banned sequence)."""
+    import math
+    bias = banned = None
+    if sequence_bias is not None:
+        sb = sequence_bias
+        if not isinstance(sb, dict) and not isinstance(sb, list) or len(sb) == 0:
+            raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sb}.")
+        if isinstance(sb, dict):
+            if any(not isinstance(seq, tuple) for seq in sb):
+                raise ValueError(f"`sequence_bias` has to be a dict with tuples as keys, but is {sb}.")
+            if any(any(not _is_token(t) or t < 0 for t in seq) or len(seq) == 0 for seq in sb):
+                raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {sb}.")
+            if any(not isinstance(b, float) for b in sb.values()):
+                raise ValueError(f"`sequence_bias` has to be a dict with floats as values, but is {sb}.")
+        else:
+            def pair_ok(e):
+                return (isinstance(e, (list, tuple)) and len(e) == 2 and isinstance(e[0], list) and len(e[0]) > 0
+                        and all(_is_token(t) and t > 0 for t in e[0]) and isinstance(e[1], float))
+            if any(not pair_ok(e) for e in sb):
+                raise ValueError(f"Each element in `sequence_bias` has to be a non-empty list of lists of positive integers and float, "
+                                 f"but is {sb}.")
+            sb = {tuple(e[0]): e[1] for e in sb}                  # (transformers' own conversion: a repeated sequence keeps its first place)
+        for seq, b in sb.items():
+            if math.isnan(b) or b == float("inf"):
+                raise ValueError(f"`sequence_bias` values have to be finite or -inf, but {seq} has {b}")
+        bias = ([tuple(int(t) for t in seq) for seq in sb], [float(b) for b in sb.values()])
+    if bad_words_ids is not None:
+        bw = bad_words_ids
+        if not isinstance(bw, list) or len(bw) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bw}.")
+        if any(not isinstance(w, list) for w in bw):
+            raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bw}.")
+        if any(any(not _is_token(t) or t < 0 for t in w) for w in bw):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bw}.")
+        if eos_token_id is not None:
+            eos = torch.as_tensor(eos_token_id).reshape(-1).tolist()
+            bw = [w for w in bw if all(w != [e] for e in eos)]
+        sb = {tuple(int(t) for t in w): float("-inf") for w in bw}
+        if any(len(seq) == 0 for seq in sb):                      # (transformers lets an empty list through; it can complete nothing)
+            raise ValueError(f"Each list in `bad_words_ids` has to be a non-empty list of positive integers, but is {bad_words_ids}.")
+        banned = (list(sb), list(sb.values())) if sb else None    # (every entry was an eos: nothing is banned, as in transformers)
+    for part in (bias, banned):
+        if part is None:
+            continue
+        if vocab_size is not None:
+            invalid = [t for seq in part[0] for t in seq if t >= vocab_size]
+            if invalid:
+                raise ValueError(f"The model vocabulary size is {vocab_size}, but the following tokens were being biased: {invalid}")
+        if len(part[0]) > L.SEQ_BIAS_MAX_SEQ or max(len(seq) for seq in part[0]) > L.SEQ_BIAS_MAX_LEN:
+            raise ValueError(f"sequence bias tables hold at most {L.SEQ_BIAS_MAX_SEQ} sequences of at most {L.SEQ_BIAS_MAX_LEN} tokens")
+    return None if bias is None and banned is None else (bias, banned)
+
+
+def sequence_bias_table(sequences, biases, device):
+    """The device table of dicow_sequence_bias (include/dicow_hip.h) for ``sequences`` (tuples of ids, distinct) and one bias each:
+    a stable sort by last token, a group's single-token sequence first, then ONE int32 buffer
+        seq_off [n + 1] | grp_off [groups + 1] | bias [n] (fp32 bits) | tok [tokens]
+    uploaded once.  Returns a namespace: buf, n_seq, n_groups, n_tokens, max_len, max_group, max_token."""
+    import numpy as np
+    seqs = [tuple(int(t) for t in s) for s in sequences]
+    if len(seqs) != len(biases) or len(set(seqs)) != len(seqs):
+        raise ValueError("sequence_bias_table: one bias per sequence, every sequence once")
+    if any(len(s) == 0 or len(s) > L.SEQ_BIAS_MAX_LEN or min(s) < 0 or max(s) >= 2 ** 31 for s in seqs) or len(seqs) > L.SEQ_BIAS_MAX_SEQ:
+        raise ValueError(f"sequence_bias_table: at most {L.SEQ_BIAS_MAX_SEQ} sequences of 1 .. {L.SEQ_BIAS_MAX_LEN} ids >= 0")
+    with np.errstate(over="ignore"):
+        b32 = np.asarray(biases, dtype=np.float32).reshape(len(seqs))
+    if not np.all(np.isfinite(b32) | np.isneginf(b32)):
+        raise ValueError("sequence_bias_table: a bias has to be finite or -inf (in fp32)")
+    order = sorted(range(len(seqs)), key=lambda i: (seqs[i][-1], len(seqs[i]) != 1))     # (stable: the caller's order within a group)
+    seq_off, grp_off, tok = [0], [], []
+    for k, i in enumerate(order):
+        if k == 0 or seqs[i][-1] != seqs[order[k - 1]][-1]:
+            grp_off.append(k)
+        tok.extend(seqs[i])
+        seq_off.append(len(tok))
+    grp_off.append(len(order))
+    n, ng = len(seqs), len(grp_off) - 1
+    flat = np.concatenate([np.asarray(seq_off, np.int32), np.asarray(grp_off, np.int32), b32[order].view(np.int32) if n else
+                           np.zeros(0, np.int32), np.asarray(tok, np.int32)])
+    return NS(buf=torch.from_numpy(flat).to(device), n_seq=n, n_groups=ng if n else 0, n_tokens=len(tok), max_len=max(map(len, seqs), default=0),
+              max_group=max((grp_off[g + 1] - grp_off[g] for g in range(ng)), default=0), max_token=max(tok, default=-1))
+
+
+def sequence_bias_rules(input_ids, scores, table, plan=0):
+    """transformers' SequenceBiasLogitsProcessor (NoBadWordsLogitsProcessor: biases of -inf) for the sequences of ``table``
+    (``sequence_bias_table``): scores fp32 [B, V] on the GPU are changed IN PLACE (and returned); input_ids int64 [B, L] = prompt +
+    generated tokens, rows may be slices of a wider buffer.  plan: 0 = the library's choice, _lib.SEQ_BIAS_LANE / _WAVE.  With an empty
+    table nothing is launched.  No CPU fallback."""
+    if not scores.is_cuda or scores.dtype != F32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise L.DicowError("sequence_bias_rules: scores must be fp32 rows on the GPU (no CPU fallback)")
+    if table is None or table.n_seq == 0:
+        return scores
+    B, V = scores.shape
+    if table.max_token >= V:
+        raise ValueError(f"The model vocabulary size is {V}, but the following tokens were being biased: [{table.max_token}]")
+    if table.buf.device != scores.device:
+        raise L.DicowError("sequence_bias_rules: the table is not on the scores' device")
+    ids = input_ids.to(device=scores.device, dtype=torch.int64)
+    if ids.dim() != 2 or ids.shape[0] != B:
+        raise L.DicowError("sequence_bias_rules: input_ids must be [rows, L] with one row per row of scores")
+    if ids.stride(1) != 1 or ids.stride(0) < ids.shape[1]:
+        ids = ids.contiguous()
+    L.call("dicow_sequence_bias", scores.data_ptr(), scores.stride(0), B, V, ids.data_ptr(), ids.stride(0), ids.shape[1],
+           table.buf.data_ptr(), table.n_seq, table.n_groups, table.n_tokens, table.max_len, table.max_group, plan, L.stream())
+    return scores
+
+
+def phrase_sequences(tokenizer, phrases, variants=("space", "plain")):
+    """Token-id tuples of every phrase for ``sequence_bias={seq: bias for seq in ...}`` or ``bad_words_ids=[list(seq) for seq in ...]``:
+    per phrase the encoding with a leading space ("space": how a BPE vocabulary spells a word inside a sentence) and as written
+    ("plain": at the start of the text), the two forms HF's documentation of the options asks for.  tokenizer: anything with
+    ``encode(text, add_special_tokens=False)``.  Distinct tuples in order of first appearance; empty encodings are left out."""
+    forms = {"space": lambda p: " " + p, "plain": lambda p: p}
+    unknown = [v for v in variants if v not in forms]
+    if unknown:
+        raise ValueError(f"phrase_sequences: unknown variants {unknown} (known: {sorted(forms)})")
+    if isinstance(phrases, str):
+        phrases = [phrases]
+    out = {}
+    for p in phrases:
+        for v in variants:
+            seq = tuple(int(t) for t in tokenizer.encode(forms[v](p), add_special_tokens=False))
+            if seq:
+                out.setdefault(seq, None)
+    return list(out)
+
+
 def advance_ancestry(anc, beam_idx, pos):
     """Ancestry table of a beam search whose self-attention caches are never reordered.  anc int32 [rows, Lmax]: anc[r, t] is the
     cache slot that holds key / value t of the hypothesis now living in row r (initially anc[r, :] = r).  After the step that
@@ -112,16 +253,21 @@ def _eos_pad(cfg, eos_token_id=None, pad_token_id=None):
 
 class ProcessorChain:
     """One window's logits processors, in the order the reference runs them: HF's own history processors in front of
-    Whisper's (``repetition_rules``), SuppressTokens / SuppressTokensAtBegin (generation.py:286-306), the timestamp rules
+    Whisper's, as transformers' _get_logits_processor orders them (``sequence_bias_rules`` on the sequence_bias table,
+    ``repetition_rules`` -- the penalty scales a score the bias has already moved --, ``sequence_bias_rules`` on the bad_words_ids
+    table), SuppressTokens / SuppressTokensAtBegin (generation.py:286-306), the timestamp rules
     (return_timestamps=True, generation.py:272-281), then the joint CTC / attention term (generation.py:249-268).
+    seqb: ``sequence_bias_options``' result; its two device tables are built here, once per window.
     ``chain(ids, scores)`` processes one step's fp32 scores [rows, V] IN PLACE given the history ids [rows, cur] = prompt
     (P tokens) + the tokens chosen so far, rows = batch x num_beams.  logprobs says what ``scores`` are: True -- already
     log-probabilities (beam search: nothing more is normalised), False -- raw logits (greedy: the log-softmax sits in front of
     the CTC term and runs only when that term is on)."""
 
-    def __init__(self, model, enc_out, prompt, eos, suppress_tokens, begin_suppress_tokens, timestamps, ctc, rep, num_beams, logprobs):
+    def __init__(self, model, enc_out, prompt, eos, suppress_tokens, begin_suppress_tokens, timestamps, ctc, rep, num_beams, logprobs,
+                 seqb=None):
         dev = enc_out.device
         self.P, self.eos, self.timestamps, self.rep, self.logprobs = prompt.shape[1], eos, timestamps, rep, logprobs
+        self.bias, self.banned = (None if part is None else sequence_bias_table(*part, dev) for part in (seqb or (None, None)))
         self.sup = None if not suppress_tokens else torch.as_tensor(list(suppress_tokens), device=dev)
         self.bsup = None if not begin_suppress_tokens else torch.as_tensor(list(begin_suppress_tokens), device=dev)
         self.rescorer = None
@@ -133,8 +279,12 @@ class ProcessorChain:
             self.rows = torch.arange(prompt.shape[0] * num_beams, device=dev)
 
     def __call__(self, ids, scores):
+        if self.bias is not None:
+            scores = sequence_bias_rules(ids, scores, self.bias)
         if self.rep is not None:
             scores = repetition_rules(ids, scores, *self.rep)
+        if self.banned is not None:
+            scores = sequence_bias_rules(ids, scores, self.banned)
         if self.sup is not None:
             scores[:, self.sup] = -float("inf")
         if self.bsup is not None and ids.shape[1] == self.P:          # the first generated position
@@ -294,7 +444,8 @@ class GreedyDecoder:
     @torch.no_grad()
     def beam_search(self, input_features, stno_mask, decoder_input_ids, max_length, num_beams, eos_token_id=None, pad_token_id=None,
                     length_penalty=1.0, early_stopping=False, suppress_tokens=None, begin_suppress_tokens=None, enrollments=None,
-                    timestamps=None, ctc=None, reorder_caches=False, repetition_penalty=None, no_repeat_ngram_size=None):
+                    timestamps=None, ctc=None, reorder_caches=False, repetition_penalty=None, no_repeat_ngram_size=None,
+                    sequence_bias=None, bad_words_ids=None):
         """Beam search as the reference runs it (DiCoWGenerationMixin._beam_search, generation.py:815-1153, on transformers'
         vectorised beam helpers): per step the top 2K continuations over beams x vocabulary, the K best unfinished keep running,
         finished ones compete for the K result slots with length-penalised scores; the ``ProcessorChain`` acts on
@@ -312,6 +463,7 @@ class GreedyDecoder:
         eos, pad = _eos_pad(cfg, eos_token_id, pad_token_id)
         reorder_caches = bool(reorder_caches) or K > L.ATTN_DECODE_MAX_GROUP
         rep = repetition_options(repetition_penalty, no_repeat_ngram_size)
+        seqb = sequence_bias_options(sequence_bias, bad_words_ids, eos, cfg.vocab_size)
         if self.use_graphs and (reorder_caches or K == 1):           # (one beam: no indirect state; refused under graphs as before)
             raise L.DicowError("beam_search(reorder_caches=True) (also: more than %d beams) copies the KV caches every step: use a "
                                "decoder without graph capture" % L.ATTN_DECODE_MAX_GROUP)
@@ -327,7 +479,7 @@ class GreedyDecoder:
         if P < 1 or P >= max_length:
             raise ValueError(f"prompt length {P} leaves no room below max_length {max_length}")
         chain = ProcessorChain(self.model, st.enc_out, prompt, eos, suppress_tokens, begin_suppress_tokens, timestamps, ctc, rep,
-                               num_beams=K, logprobs=True)
+                               num_beams=K, logprobs=True, seqb=seqb)
         fill = pad if pad is not None else eos
         run_seq = torch.full((B, K, max_length), fill, dtype=torch.long, device=dev)
         run_seq[:, :, :P] = prompt[:, None, :]
@@ -394,9 +546,10 @@ class GreedyDecoder:
     def generate(self, input_features, stno_mask, decoder_input_ids, max_new_tokens, eos_token_id=None, pad_token_id=None,
                  suppress_tokens=None, begin_suppress_tokens=None, enrollments=None, return_scores=False, ctc=None,
                  timestamps=None, temperature=0.0, generator=None, no_speech_token_id=None, repetition_penalty=None,
-                 no_repeat_ngram_size=None):
+                 no_repeat_ngram_size=None, sequence_bias=None, bad_words_ids=None):
         """decoder_input_ids int64 [B, P]: the forced prefix (start token, language / task / timestamp tokens).
-        The step's raw logits go through the ``ProcessorChain``: repetition_penalty / no_repeat_ngram_size, the suppress lists,
+        The step's raw logits go through the ``ProcessorChain``: sequence_bias, repetition_penalty / no_repeat_ngram_size,
+        bad_words_ids (HF's options of those names, see ``sequence_bias_options``), the suppress lists,
         timestamps: dict(no_timestamps_token_id=..., max_initial_timestamp_index=...) for Whisper's timestamp rules, and
         ctc: dict(weight=..., first_timestamp=..., upper_cased=[(lo, up), ...], prefix_len=..., n_score=500) for the joint
         CTC / attention scoring (log-softmax, then ctc_decoding.CtcRescorer on the model's CTC head).
@@ -407,6 +560,7 @@ class GreedyDecoder:
         Returns sequences [B, P + n] (and the processed fp32 scores [n, B, V] of the generated positions)."""
         cfg = self.cfg
         eos, pad = _eos_pad(cfg, eos_token_id, pad_token_id)
+        seqb = sequence_bias_options(sequence_bias, bad_words_ids, eos, cfg.vocab_size)
         st = self.encode(input_features, stno_mask, enrollments)
         dev = st.enc_out.device
         ids = decoder_input_ids.to(dev)
@@ -414,7 +568,7 @@ class GreedyDecoder:
         if P < 1 or P + max_new_tokens > cfg.max_target_positions:
             raise ValueError(f"prompt {P} + max_new_tokens {max_new_tokens} exceeds max_target_positions {cfg.max_target_positions}")
         chain = ProcessorChain(self.model, st.enc_out, ids, eos, suppress_tokens, begin_suppress_tokens, timestamps, ctc,
-                               repetition_options(repetition_penalty, no_repeat_ngram_size), num_beams=1, logprobs=False)
+                               repetition_options(repetition_penalty, no_repeat_ngram_size), num_beams=1, logprobs=False, seqb=seqb)
         step = self._step_graphed if self.use_graphs else self._step
         self.no_speech_prob = None
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
@@ -455,7 +609,8 @@ class GreedyDecoder:
         generate_with_fallback): greedy first; windows whose output is too repetitive (zlib compression ratio) or too unlikely
         (average log-probability) are decoded again -- encoder included, as in HF -- with sampling at the next temperature; a
         window that is unlikely AND looks like silence (no_speech_prob) is skipped instead.  gen_kw: generate()'s processor
-        arguments (eos / pad ids, suppress lists, timestamps, ctc, repetition_penalty, no_repeat_ngram_size).
+        arguments (eos / pad ids, suppress lists, timestamps, ctc, repetition_penalty, no_repeat_ngram_size, sequence_bias,
+        bad_words_ids).
         Returns (token lists of the generated positions without the eos, should_skip flags, temperature index per window)."""
         eos, pad = _eos_pad(self.cfg, gen_kw.get("eos_token_id"), gen_kw.get("pad_token_id"))
         B, P = decoder_input_ids.shape
@@ -697,8 +852,8 @@ class LongFormDecoder:
                    pad_token_id=None, max_new_tokens=None, enrollments=None, **gen_kw):
         """input_features [B, M, T_total] (T_total a multiple of nothing in particular), stno_mask [B, 4, T_total / 2],
         max_frames [B] valid feature frames per recording, decoder_input_ids [1 or B, P] the forced prompt.
-        gen_kw: suppress_tokens, begin_suppress_tokens, max_initial_timestamp_index, ctc, repetition_penalty and
-        no_repeat_ngram_size (every window's history starts from that window's prompt, as in HF), the fallback arguments, and for
+        gen_kw: suppress_tokens, begin_suppress_tokens, max_initial_timestamp_index, ctc, repetition_penalty, no_repeat_ngram_size,
+        sequence_bias and bad_words_ids (every window's history starts from that window's prompt, as in HF), the fallback arguments, and for
         num_beams > 1 length_penalty, early_stopping and reorder_caches (False: beam_search's default beam-indirect caches; True: its
         former copying path).
         Returns per recording a list of segments dict(start, end, tokens) in seconds / token ids."""
@@ -716,7 +871,8 @@ class LongFormDecoder:
         # the decoder's keywords, the same for every window (only ``enrollments`` is cut to the active rows inside the loop)
         ts = dict(no_timestamps_token_id=no_timestamps_token_id, max_initial_timestamp_index=gen_kw.get("max_initial_timestamp_index", 50))
         kw = dict(eos_token_id=eos, pad_token_id=pad, timestamps=ts,
-                  **{k: gen_kw.get(k) for k in ("suppress_tokens", "begin_suppress_tokens", "ctc", "repetition_penalty", "no_repeat_ngram_size")})
+                  **{k: gen_kw.get(k) for k in ("suppress_tokens", "begin_suppress_tokens", "ctc", "repetition_penalty", "no_repeat_ngram_size",
+                                                      "sequence_bias", "bad_words_ids")})
         ladder = gen_kw.get("temperatures") is not None and self.num_beams == 1
         if ladder:
             # temperature fallback (reference generation.py:567-611): per-window ladder, silent windows skipped (skip_by_row=True

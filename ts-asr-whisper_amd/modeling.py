@@ -775,9 +775,9 @@ class DiCoWForConditionalGeneration(_ModelBase):
         (generation.LongFormDecoder) and the window-relative sequences of _fix_timestamps_from_segmentation.
         ``generation_config``: any object with the HF / reference attribute names (eos_token_id, pad_token_id, suppress_tokens,
         begin_suppress_tokens, return_timestamps, no_timestamps_token_id, max_initial_timestamp_index, ctc_weight,
-        repetition_penalty, no_repeat_ngram_size, ...).
+        repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, ...).
         The prompt is ``decoder_input_ids`` or [decoder_start_token_id] + the tokenizer's prefix tokens."""
-        from .generation import repetition_options
+        from .generation import repetition_options, sequence_bias_options
         gc = generation_config if generation_config is not None else self.generation_config
         # (explicit keyword arguments win over the generation config, as in HF's generate)
         # -- except `temperature`, which HF's WhisperGenerationMixin.generate (the method the reference delegates to) takes from
@@ -821,6 +821,10 @@ class DiCoWForConditionalGeneration(_ModelBase):
         # bad value raises before any window is decoded
         rep_kw = dict(repetition_penalty=get("repetition_penalty"), no_repeat_ngram_size=get("no_repeat_ngram_size"))
         repetition_options(**rep_kw)
+        # HF's sequence_bias / bad_words_ids (generation.sequence_bias_rules, around the repetition rules), validated here likewise
+        rep_kw.update(sequence_bias=get("sequence_bias"), bad_words_ids=get("bad_words_ids"))
+        sequence_bias_options(rep_kw["sequence_bias"], rep_kw["bad_words_ids"], get("eos_token_id", self.config.eos_token_id),
+                              self.config.vocab_size)
         if takes_seek_loop:
             if one_window_seek and attention_mask is None:
                 attention_mask = torch.ones(input_features.shape[0], n_frames, dtype=torch.long, device=input_features.device)
