@@ -936,6 +936,56 @@ int dicow_repetition_rules(float* scores, int64_t ld, int rows, int V, const int
 int dicow_sequence_bias(float* scores, int64_t ld, int rows, int V, const int64_t* input_ids, int64_t ids_stride, int L,
                         const int* table, int n_seq, int n_groups, int n_tokens, int max_len, int max_group, int plan, void* stream);
 
+/* Sampling a step's next tokens (ABI 7, additive): the warpers HF's generate builds for do_sample=True (TemperatureLogitsWarper,
+ * TopKLogitsWarper, TopPLogitsWarper, MinPLogitsWarper, min_tokens_to_keep = 1), the draw, the chosen token's log-probability and the
+ * end-of-sequence bookkeeping of a greedy / sampling loop, ONE launch over the processed scores fp32 [rows, ld >= V] (read only).
+ * Below x_v = scores[r, v] with NaN read as -inf; temperature, top_p and min_p are the fp32 numbers of the struct; tokens are compared
+ * as fp32 numbers (-0.0 == +0.0).
+ * Warpers.
+ *   temperature   y_v = x_v / temperature, one correctly rounded fp32 division.  temperature <= 0 (the argmax rung): y = x and no warper
+ *                 is applied, whatever top_k / top_p / min_p hold.
+ *   top_k (<= 0: off)   k = min(top_k, V); v is removed iff y_v < the k-th largest y (ties with the k-th value stay; with fewer than k
+ *                 finite scores nothing finite is removed).  Exact: counting only.
+ *   top_p (>= 1: off)   over the tokens top_k kept, e_v = exp(y_v - y_max), Z = sum e; v is removed iff
+ *                 sum{e_u : y_u <= y_v} <= (1 - top_p) * Z; the maximum is always kept.  A tie class is kept or removed as a whole.  The
+ *                 e_v are fp32 (one exp2 of an fp32 product each), summed in fp64 in a fixed order; 1 - top_p is formed in fp64.
+ *   min_p (<= 0: off)   v is removed iff exp(y_v - y_max) < min_p over what is left, evaluated in fp64.
+ *   -inf scores are removed tokens from the start.  All three rules cut the order of y from below, so the kept set is
+ *   {v : y_v >= a threshold}; `warped` (fp32 [rows, ld_w >= V] or NULL) receives y_v for kept tokens and -inf for the others -- the
+ *   scores HF returns.  Columns >= V are not touched.
+ * The draw.
+ *   temperature <= 0: the lowest index of the maximum of x.
+ *   otherwise Gumbel-max:  w(v) = Philox4x32-10(counter = (v >> 2, row_id, step, stream), key = (seed lo, seed hi))[v & 3], row_id = the
+ *   low 32 bits of row_ids[r] (r itself when row_ids is NULL);  u = ((w >> 8) + 0.5) * 2^-24, strictly inside (0, 1);  the token is the
+ *   argmax over kept v of y_v - log(-log(u)), lowest index on ties.  (u is an fp32 number for w >> 8 < 2^23 only; above, -log(u) is
+ *   evaluated as -log1p(-(1 - u)), 1 - u = ((2^24 - 1 - (w >> 8)) + 0.5) * 2^-24 being one.  The two logarithms are fp32.)  A row's
+ *   token is a function of (its scores, the options, seed, row_id, step, stream) alone: not of the grid, the plan or the other rows.
+ * Bookkeeping.
+ *   next[r * next_stride] (int64) = the token.  logprob[r] (fp32, or NULL) = x_tok - logsumexp{x_v : v kept}: the token's log-probability
+ *   at temperature 1 over the kept set (fp32 exps summed in fp64, one fp32 rounding at the end: within 2^-22 |lp| + 70 * 2^-24 of the
+ *   exact value, the budget also behind the top_p band 2e-5 of the tests).
+ *   unfinished (uint8 [rows], in/out, or NULL): a row whose flag is 0 writes `pad`, logprob 0, and keeps the flag; a row that draws `eos`
+ *   clears its flag.  A row without any score above -inf writes `eos` (and clears its flag), logprob NaN, `warped` all -inf.
+ * One workgroup of 1024 lanes per row; lane l owns tokens l, l + 1024, ...; every sum and count is reduced in a fixed order (lane-serial,
+ * wave butterfly, 16 waves in order); integers and fp64 masses decide the thresholds by bisection over the order-preserving 32-bit key
+ * of y.  No atomics, one writer per element, no workspace, capturable.
+ * plan: 0 = the library's choice (REG when V <= DICOW_SAMPLE_REG_MAX_V), DICOW_SAMPLE_REG = the row is read once and held in registers,
+ * DICOW_SAMPLE_STREAM = every pass re-reads the row (any V).  Both give identical bits in every output.
+ * Refused before anything is launched (-1, dicow_last_error() names the limit): an unknown plan, DICOW_SAMPLE_REG with
+ * V > DICOW_SAMPLE_REG_MAX_V, rows < 0, V < 1, ld < V, ld_w < V, next == NULL, a NaN option.  rows == 0 launches nothing. */
+#define DICOW_SAMPLE_REG_MAX_V 65536
+#define DICOW_SAMPLE_PLANS 2
+#define DICOW_SAMPLE_REG 1
+#define DICOW_SAMPLE_STREAM 2
+typedef struct {
+    const float* scores; int64_t ld; int rows; int V;
+    float temperature; int top_k; float top_p; float min_p;
+    uint64_t seed; uint32_t step; uint32_t stream;
+    const int64_t* row_ids; uint8_t* unfinished; int eos; int pad;
+    int64_t* next; int64_t next_stride; float* logprob; float* warped; int64_t ld_w; int plan;
+} dicow_sample_args;
+int dicow_sample_tokens(const dicow_sample_args* a, void* stream);
+
 /* Greedy CTC decoding (ABI 7, additive): ctc_greedy_decode of the reference (src/utils/decoding.py:6-12: torch.argmax, then a Python
  * itertools.groupby over every row of the device tensor), the preprocess_logits_for_metrics of CTC pre-training (src/pretrain_encoder.py:82-86).
  * logits fp32 / bf16 (in_bf16): frame t of batch row b starts at element b * batch_stride + t * ld; unit stride over the V1 <= ld classes.  The

@@ -13,7 +13,7 @@ from .modeling import (FDDT, DiCoWEncoder, DiCoW, DiCoWForConditionalGeneration,
                        shift_tokens_right, build_ts_tables, LoRALinear, add_decoder_lora, merge_lora, save_adapter, load_adapter,
                        freeze_for_ctc_pretraining)
 from .ctc_decoding import ctc_greedy_decode, chunked_ctc_logits  # noqa: F401
-from .generation import phrase_sequences  # noqa: F401
+from .generation import phrase_sequences, sample_tokens, sampling_options  # noqa: F401
 from .ctc_align import (CtcAlignment, ctc_forced_align, token_timestamps, word_timestamps, align_segments,  # noqa: F401
                         words_as_segments)
 from .wave_augment import NoiseBank, plan_background_noise, mix_background_noise, WaveFrontEnd  # noqa: F401
@@ -52,4 +52,4 @@ __all__ = ["DiCoWConfig", "FDDT", "DiCoWEncoder", "DiCoW", "DiCoWForConditionalG
            "score_diarizations", "CtcAlignment", "ctc_forced_align", "token_timestamps", "word_timestamps", "align_segments",
            "words_as_segments", "tensor_stats", "TensorStats", "GradWatch", "WatchCallback", "as_wandb", "jsonl_sink", "repeating_ngram_cuts", "truncate_repeating_ngrams", "truncate_at_repeating_ngram", "session_hypotheses",
            "bootstrap_sums", "percentile_interval", "ratio_interval", "compare_ratios", "session_metric_intervals", "compare_session_metrics",
-           "wer_interval", "compare_wer", "phrase_sequences"]
+           "wer_interval", "compare_wer", "phrase_sequences", "sample_tokens", "sampling_options"]

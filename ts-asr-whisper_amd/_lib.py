@@ -104,6 +104,18 @@ BOOT_RESAMPLE, BOOT_SWAP = 0, 1
 # DICOW_SEQ_BIAS_*: dicow_sequence_bias's longest history, longest sequence, most sequences, and its plans
 SEQ_BIAS_MAX_L, SEQ_BIAS_MAX_LEN, SEQ_BIAS_MAX_SEQ, SEQ_BIAS_PLANS, SEQ_BIAS_LANE, SEQ_BIAS_WAVE = 8192, 32, 65536, 2, 1, 2
 
+# DICOW_SAMPLE_*: dicow_sample_tokens's widest row under the register plan, and its plans
+SAMPLE_REG_MAX_V, SAMPLE_PLANS, SAMPLE_REG, SAMPLE_STREAM = 65536, 2, 1, 2
+
+
+class SampleArgs(C.Structure):
+    _fields_ = [("scores", c_vp), ("ld", c_i64), ("rows", c_i), ("V", c_i),
+                ("temperature", c_f), ("top_k", c_i), ("top_p", c_f), ("min_p", c_f),
+                ("seed", c_u64), ("step", C.c_uint32), ("stream", C.c_uint32),
+                ("row_ids", c_vp), ("unfinished", c_vp), ("eos", c_i), ("pad", c_i),
+                ("next", c_vp), ("next_stride", c_i64), ("logprob", c_vp), ("warped", c_vp), ("ld_w", c_i64), ("plan", c_i)]
+
+
 LORA_MAX_R, LORA_MAX_SEG = 192, 24
 LORA_BLOCK, LORA_OUT_F32, LORA_GELU, LORA_MUL_AUX = 1, 2, 4, 8
 
@@ -221,6 +233,7 @@ _SIGS = {
     "dicow_whisper_timestamp_rules": [c_vp, c_i64, c_i, c_i, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
     "dicow_repetition_rules": [c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_i, c_f, c_i, c_vp],
     "dicow_sequence_bias": [c_vp, c_i64, c_i, c_i, c_vp, c_i64, c_i, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
+    "dicow_sample_tokens": [C.POINTER(SampleArgs), c_vp],
     "dicow_ctc_greedy_decode": [c_vp, c_i, c_i64, c_i64, c_i, c_i, c_i, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp],
     "dicow_ctc_forced_align": [c_vp, c_i, c_i, c_i, c_i, c_i64, c_vp, c_vp, c_i, c_vp, c_i, c_vp, c_i64, c_vp, c_i, c_vp, c_i, c_vp, c_vp, c_vp,
                                c_i, c_vp, c_i64, c_vp],

@@ -5,6 +5,8 @@
   * ``timestamp_rules``, ``repetition_rules``   Whisper's timestamp processor and HF's two history processors, one kernel each;
   * ``sequence_bias_rules``  HF's sequence_bias / bad_words_ids (hotwords, banned phrases): one kernel over a device table
                             (``sequence_bias_options``, ``sequence_bias_table``; ``phrase_sequences`` turns phrases into ids);
+  * ``sample_tokens``       HF's sampling warpers (temperature, top_k, top_p, min_p), a counter-addressed Philox / Gumbel-max draw, the
+                            token's log-probability and the end-of-sequence flags: one kernel behind the chain (``sampling_options``);
   * ``ProcessorChain``      the ONE place that orders a step's processors -- sequence bias, repetition rules, banned phrases,
                             suppress lists, timestamp rules, joint CTC / attention term (ctc_decoding.CtcRescorer) -- for greedy
                             and beam decoding alike;
@@ -210,6 +212,73 @@ def sequence_bias_rules(input_ids, scores, table, plan=0):
     L.call("dicow_sequence_bias", scores.data_ptr(), scores.stride(0), B, V, ids.data_ptr(), ids.stride(0), ids.shape[1],
            table.buf.data_ptr(), table.n_seq, table.n_groups, table.n_tokens, table.max_len, table.max_group, plan, L.stream())
     return scores
+
+
+MAX_LADDER_RUNGS = 16                 # the sampler's stream word is seek-loop iteration * 16 + rung
+
+
+def sampling_options(top_k=None, top_p=None, min_p=None, seed=None, generator=None):
+    """Validation of the sampling arguments, once per call: ``top_k`` an int >= 0 (0: off), ``top_p`` in (0, 1] (1: off), ``min_p`` in
+    [0, 1] (0: off), ``seed`` an int in [0, 2^64) -- the key of the sampler's own Philox stream, which replaces ``generator`` (both
+    given: ValueError).  Returns None when all four are None (the caller keeps its torch path), else a namespace
+    (top_k, top_p, min_p, seed) as ``sample_tokens`` takes them."""
+    if top_k is None and top_p is None and min_p is None and seed is None:
+        return None
+    if seed is not None and generator is not None:
+        raise ValueError("`seed` keys the device sampler's own Philox stream; it cannot be combined with `generator`")
+    if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0):
+        raise ValueError(f"`top_k` has to be a non-negative integer, but is {top_k}")
+    if top_p is not None and (isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0.0 < float(top_p) <= 1.0):
+        raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
+    if min_p is not None and (isinstance(min_p, bool) or not isinstance(min_p, (int, float)) or not 0.0 <= float(min_p) <= 1.0):
+        raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64):
+        raise ValueError(f"`seed` has to be an integer in [0, 2^64), but is {seed}")
+    return NS(top_k=top_k or 0, top_p=1.0 if top_p is None else float(top_p), min_p=0.0 if min_p is None else float(min_p),
+              seed=seed or 0)
+
+
+def sample_tokens(scores, temperature=0.0, top_k=0, top_p=1.0, min_p=0.0, seed=0, step=0, stream=0, row_ids=None, unfinished=None,
+                  eos_token_id=-1, pad_token_id=0, out=None, logprob=None, warped=None, plan=0):
+    """dicow_sample_tokens (include/dicow_hip.h): one launch that warps the processed scores fp32 [rows, V] (read only; rows may be
+    slices of a wider buffer) with temperature / top_k / top_p / min_p as HF's warpers do, draws every row's token -- the argmax when
+    temperature <= 0, else a Gumbel-max draw addressed by (seed, row_ids[r] or r, step, stream) -- and writes it into ``out`` (int64
+    [rows], any stride: e.g. a column of the token history; allocated when None), which is returned.
+    logprob: fp32 [rows] that receives the token's log-probability over the kept set at temperature 1; warped: fp32 [rows, >= V] rows
+    that receive the warped scores (-inf outside the kept set); unfinished: bool / uint8 [rows] flags, updated in place: a finished row
+    writes ``pad_token_id``, a row that draws ``eos_token_id`` is cleared.  plan: 0 = the library's choice, _lib.SAMPLE_REG / _STREAM.
+    No CPU fallback."""
+    if not scores.is_cuda or scores.dtype != F32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise L.DicowError("sample_tokens: scores must be fp32 rows on the GPU (no CPU fallback)")
+    rows, V = scores.shape
+    dev = scores.device
+    if out is None:
+        out = torch.empty(rows, dtype=torch.long, device=dev)
+
+    def dev_tensor(t, dtypes, what, shape=(rows,)):
+        if t is None:
+            return None
+        if t.device != dev or t.dtype not in dtypes or tuple(t.shape[:1]) != shape[:1] or t.dim() != len(shape):
+            raise L.DicowError(f"sample_tokens: {what} must be a {dtypes[0]} tensor of {len(shape)} dimension(s) over the rows, on the scores' device")
+        return t
+
+    dev_tensor(out, (torch.int64,), "out")
+    if dev_tensor(logprob, (F32,), "logprob") is not None and rows > 1 and logprob.stride(0) != 1:
+        raise L.DicowError("sample_tokens: logprob must be contiguous")
+    if dev_tensor(unfinished, (torch.bool, torch.uint8), "unfinished") is not None and rows > 1 and unfinished.stride(0) != 1:
+        raise L.DicowError("sample_tokens: unfinished must be contiguous")
+    if dev_tensor(warped, (F32,), "warped", (rows, V)) is not None and (warped.shape[1] < V or warped.stride(1) != 1):
+        raise L.DicowError("sample_tokens: warped must be fp32 rows of at least V columns")
+    if row_ids is not None:
+        row_ids = dev_tensor(torch.as_tensor(row_ids, dtype=torch.int64, device=dev).contiguous(), (torch.int64,), "row_ids")
+    a = L.SampleArgs(scores=scores.data_ptr(), ld=scores.stride(0) if rows > 1 else max(scores.stride(0), V), rows=rows, V=V,
+                     temperature=float(temperature or 0.0), top_k=int(top_k), top_p=float(top_p), min_p=float(min_p),
+                     seed=int(seed), step=int(step), stream=int(stream), row_ids=L.ptr(row_ids), unfinished=L.ptr(unfinished),
+                     eos=-1 if eos_token_id is None else int(eos_token_id), pad=int(pad_token_id or 0), next=out.data_ptr(),
+                     next_stride=out.stride(0) if rows > 1 else 1, logprob=L.ptr(logprob), warped=L.ptr(warped),
+                     ld_w=0 if warped is None else (warped.stride(0) if rows > 1 else max(warped.stride(0), V)), plan=int(plan))
+    L.call_struct("dicow_sample_tokens", a)
+    return out
 
 
 def phrase_sequences(tokenizer, phrases, variants=("space", "plain")):
@@ -546,7 +615,8 @@ class GreedyDecoder:
     def generate(self, input_features, stno_mask, decoder_input_ids, max_new_tokens, eos_token_id=None, pad_token_id=None,
                  suppress_tokens=None, begin_suppress_tokens=None, enrollments=None, return_scores=False, ctc=None,
                  timestamps=None, temperature=0.0, generator=None, no_speech_token_id=None, repetition_penalty=None,
-                 no_repeat_ngram_size=None, sequence_bias=None, bad_words_ids=None):
+                 no_repeat_ngram_size=None, sequence_bias=None, bad_words_ids=None, top_k=None, top_p=None, min_p=None, seed=None,
+                 row_ids=None, stream=0, return_logprobs=False):
         """decoder_input_ids int64 [B, P]: the forced prefix (start token, language / task / timestamp tokens).
         The step's raw logits go through the ``ProcessorChain``: sequence_bias, repetition_penalty / no_repeat_ngram_size,
         bad_words_ids (HF's options of those names, see ``sequence_bias_options``), the suppress lists,
@@ -557,10 +627,22 @@ class GreedyDecoder:
         temperature fallback decodes with; `generator` makes it reproducible); the returned scores are then the temperature-scaled
         ones, as HF's are.  no_speech_token_id: also keep softmax(logits of the position after the start token)[that id] per row
         in ``self.no_speech_prob`` (HF WhisperNoSpeechDetection).
-        Returns sequences [B, P + n] (and the processed fp32 scores [n, B, V] of the generated positions)."""
+        top_k / top_p / min_p / seed (``sampling_options``), row_ids, return_logprobs: any of them moves the step's tail -- warpers,
+        draw, log-probability, end-of-sequence flags -- into ONE ``sample_tokens`` launch that writes the token straight into the
+        history.  The draw at history position t of row r is then addressed by (seed, row_ids[r] or r, t, stream), whatever else is in
+        the batch; at temperature 0 it is the argmax.  return_logprobs: also return the chosen tokens' log-probabilities [n, B]
+        (over the kept set, at temperature 1: what ``sequence_avg_logprob`` recovers from the scores) without keeping any [n, B, V]
+        tensor; return_scores then returns the WARPED scores (-inf outside the kept set), as HF does.
+        Returns sequences [B, P + n] (and the processed fp32 scores [n, B, V] of the generated positions; and the fp32
+        log-probabilities [n, B])."""
         cfg = self.cfg
         eos, pad = _eos_pad(cfg, eos_token_id, pad_token_id)
         seqb = sequence_bias_options(sequence_bias, bad_words_ids, eos, cfg.vocab_size)
+        sopt = sampling_options(top_k, top_p, min_p, seed, generator)
+        on_device = sopt is not None or row_ids is not None or return_logprobs
+        if on_device and generator is not None:
+            raise ValueError("`generator` drives torch.multinomial; the device sampler (top_k / top_p / min_p / seed / row_ids / "
+                             "return_logprobs) draws from its own Philox stream: pass `seed`")
         st = self.encode(input_features, stno_mask, enrollments)
         dev = st.enc_out.device
         ids = decoder_input_ids.to(dev)
@@ -575,6 +657,9 @@ class GreedyDecoder:
         hist = torch.empty(B, P + max_new_tokens, dtype=torch.long, device=dev)    # the token history: position t sees hist[:, :t + 1]
         hist[:, :P] = ids
         scores, end, cur = [], P, ids[:, 0]
+        if on_device:                                                # the step's tail is one launch (``_generate_on_device``)
+            return self._generate_on_device(step, st, chain, hist, P, max_new_tokens, eos, pad, temperature, sopt or sampling_options(seed=0),
+                                            row_ids, stream, no_speech_token_id, return_scores, return_logprobs)
         for t in range(P - 1 + max_new_tokens):
             logits = step(cur, t, st)
             if t == 0 and no_speech_token_id is not None:            # the position after the start token, before any processor
@@ -601,25 +686,78 @@ class GreedyDecoder:
         out = hist[:, :end].clone()                                  # contiguous, and its own storage
         return (out, torch.stack(scores)) if return_scores else out
 
+    def _generate_on_device(self, step, st, chain, hist, P, max_new_tokens, eos, pad, temperature, sopt, row_ids, stream, no_speech_token_id,
+                            return_scores, return_logprobs):
+        """generate()'s loop with ``sample_tokens`` as the step's tail: the kernel reads the processed scores, writes the token into
+        hist[:, t + 1] and keeps the unfinished flags; the host reads one ``.any()`` of them per step, as the torch loop does."""
+        B, V, dev = hist.shape[0], self.cfg.vocab_size, hist.device
+        flags = torch.ones(B, dtype=torch.uint8, device=dev)
+        lps = torch.zeros(max_new_tokens, B, dtype=F32, device=dev) if return_logprobs else None
+        rid = None if row_ids is None else torch.as_tensor(row_ids, dtype=torch.int64, device=dev).contiguous()
+        if rid is not None and tuple(rid.shape) != (B,):
+            raise ValueError(f"row_ids must hold one id per row ({B}), but has shape {tuple(rid.shape)}")
+        scores, end, cur = [], P, hist[:, 0]
+        for t in range(P - 1 + max_new_tokens):
+            logits = step(cur, t, st)
+            if t == 0 and no_speech_token_id is not None:            # the position after the start token, before any processor
+                self.no_speech_prob = torch.softmax(logits.float(), dim=-1)[:, no_speech_token_id].clone()
+            cur = hist[:, t + 1]
+            if t < P - 1:                                            # inside the forced prefix: the step only fills the caches
+                continue
+            logits = chain(hist[:, :t + 1], logits)
+            if logits.dtype != F32 or logits.stride(1) != 1:
+                logits = logits.float().contiguous()
+            warped = torch.empty(B, V, dtype=F32, device=dev) if return_scores else None
+            sample_tokens(logits, temperature, sopt.top_k, sopt.top_p, sopt.min_p, sopt.seed, step=t + 1, stream=stream, row_ids=rid,
+                          unfinished=flags, eos_token_id=eos, pad_token_id=pad, out=cur, logprob=None if lps is None else lps[t + 1 - P],
+                          warped=warped)
+            if return_scores:
+                scores.append(warped)
+            chain.advance(cur)
+            end = t + 2
+            if not bool(flags.any()):
+                break
+        out = hist[:, :end].clone()                                  # contiguous, and its own storage
+        return (out,) + ((torch.stack(scores),) if return_scores else ()) + ((lps[:end - P].clone(),) if return_logprobs else ())
+
     @torch.no_grad()
     def generate_with_fallback(self, input_features, stno_mask, decoder_input_ids, max_new_tokens, temperatures=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
                                compression_ratio_threshold=1.35, logprob_threshold=-1.0, no_speech_threshold=None,
-                               no_speech_token_id=None, generator=None, enrollments=None, skip_by_row=False, **gen_kw):
+                               no_speech_token_id=None, generator=None, enrollments=None, skip_by_row=False, top_k=None, top_p=None,
+                               min_p=None, seed=None, row_ids=None, stream=0, **gen_kw):
         """Whisper's temperature fallback over one batch of windows (reference generation.py:567-611 -> transformers'
         generate_with_fallback): greedy first; windows whose output is too repetitive (zlib compression ratio) or too unlikely
         (average log-probability) are decoded again -- encoder included, as in HF -- with sampling at the next temperature; a
         window that is unlikely AND looks like silence (no_speech_prob) is skipped instead.  gen_kw: generate()'s processor
         arguments (eos / pad ids, suppress lists, timestamps, ctc, repetition_penalty, no_repeat_ngram_size, sequence_bias,
         bad_words_ids).
+        top_k / top_p / min_p / seed (``sampling_options``): the rungs decode through ``sample_tokens`` -- HF's warpers on every rung
+        with temperature > 0 -- and the log-probability test reads the kernel's token log-probabilities (no [n, B, V] scores are
+        kept).  A window's draws are addressed by its id -- row_ids[window], default its index in this batch -- and by the stream
+        word ``stream + rung`` (at most MAX_LADDER_RUNGS rungs), so they do not depend on which other windows fall back with it.
         Returns (token lists of the generated positions without the eos, should_skip flags, temperature index per window)."""
         eos, pad = _eos_pad(self.cfg, gen_kw.get("eos_token_id"), gen_kw.get("pad_token_id"))
         B, P = decoder_input_ids.shape
+        sopt = sampling_options(top_k, top_p, min_p, seed, generator)
+        if sopt is not None or row_ids is not None:
+            if len(temperatures) > MAX_LADDER_RUNGS:
+                raise ValueError(f"the device sampler addresses at most {MAX_LADDER_RUNGS} rungs, but the ladder has {len(temperatures)}")
+            wid = list(range(B)) if row_ids is None else [int(i) for i in row_ids]
+            if len(wid) != B:
+                raise ValueError(f"row_ids must hold one id per window ({B}), but has {len(wid)}")
+            rung = iter(range(len(temperatures)))
         if no_speech_threshold is not None and no_speech_token_id is None:
             raise ValueError("no_speech_threshold needs no_speech_token_id")
 
         def decode(rows, temperature):
             idx = torch.as_tensor(rows, device=input_features.device)
             enr = None if enrollments is None else {k: v[idx] for k, v in enrollments.items()}
+            if sopt is not None or row_ids is not None:
+                seqs, lps = self.generate(input_features[idx], stno_mask[idx], decoder_input_ids[idx.to(decoder_input_ids.device)],
+                                          max_new_tokens, enrollments=enr, temperature=temperature, no_speech_token_id=no_speech_token_id,
+                                          top_k=top_k, top_p=top_p, min_p=min_p, seed=seed, row_ids=[wid[i] for i in rows],
+                                          stream=stream + next(rung), return_logprobs=True, **gen_kw)
+                return seqs[:, P:].tolist(), [lps[:, i] for i in range(len(rows))], self.no_speech_prob
             seqs, scores = self.generate(input_features[idx], stno_mask[idx], decoder_input_ids[idx.to(decoder_input_ids.device)],
                                          max_new_tokens, enrollments=enr, return_scores=True, temperature=temperature,
                                          generator=generator, no_speech_token_id=no_speech_token_id, **gen_kw)
@@ -656,13 +794,24 @@ def sequence_avg_logprob(scores, tokens, temperature):
     return float(lp.gather(1, tk[:, None]).sum() / tok.numel())
 
 
+def sequence_avg_logprob_from_tokens(logprobs, tokens):
+    """``sequence_avg_logprob`` from the generated tokens' own log-probabilities: logprobs [n] as generate(return_logprobs=True)
+    returns them for one window (taken over the kept set at temperature 1, which is what the log-softmax of the warped scores times
+    the temperature gives).  The same alignment rule: with fewer positions than tokens the LAST n tokens are the scored ones."""
+    n_tok = len(list(tokens))
+    n = min(int(logprobs.shape[0]), n_tok)
+    return float(logprobs[:n].float().sum() / n_tok)
+
+
 def window_needs_fallback(tokens, scores, temperature, vocab_size, compression_ratio_threshold, logprob_threshold,
                           no_speech_threshold=None, no_speech_prob=None):
-    """(needs_fallback, should_skip) of one decoded window (HF _need_fallback)."""
+    """(needs_fallback, should_skip) of one decoded window (HF _need_fallback).  scores: the window's [n, V] processed scores, or the
+    1-D vector of its tokens' log-probabilities."""
     needs = compression_ratio_threshold is not None and token_compression_ratio(tokens, vocab_size) > compression_ratio_threshold
     low = False
     if logprob_threshold is not None:
-        low = sequence_avg_logprob(scores, tokens, temperature) < logprob_threshold
+        avg = sequence_avg_logprob_from_tokens(scores, tokens) if scores.dim() == 1 else sequence_avg_logprob(scores, tokens, temperature)
+        low = avg < logprob_threshold
         needs = needs or low
     if no_speech_threshold is not None and low and no_speech_prob is not None and no_speech_prob > no_speech_threshold:
         return False, True
@@ -672,7 +821,7 @@ def window_needs_fallback(tokens, scores, temperature, vocab_size, compression_r
 def decode_with_fallback(decode, n_windows, temperatures, vocab_size, pad_token_id, eos_token_id, compression_ratio_threshold=1.35,
                          logprob_threshold=-1.0, no_speech_threshold=None, skip_by_row=False):
     """Temperature ladder over a batch of windows.  decode(rows, temperature) -> (token lists of the generated positions,
-    [n, V] score tensors, no-speech probabilities or None) for the listed windows.  Every window keeps its latest result;
+    [n, V] score tensors -- or 1-D vectors of the tokens' log-probabilities --, no-speech probabilities or None) for the listed windows.  Every window keeps its latest result;
     those that fail the compression / log-probability test are decoded again at the next temperature.
     Returns (token lists without the eos, should_skip flags, index of the temperature each window ended with).
 
@@ -853,7 +1002,9 @@ class LongFormDecoder:
         """input_features [B, M, T_total] (T_total a multiple of nothing in particular), stno_mask [B, 4, T_total / 2],
         max_frames [B] valid feature frames per recording, decoder_input_ids [1 or B, P] the forced prompt.
         gen_kw: suppress_tokens, begin_suppress_tokens, max_initial_timestamp_index, ctc, repetition_penalty, no_repeat_ngram_size,
-        sequence_bias and bad_words_ids (every window's history starts from that window's prompt, as in HF), the fallback arguments, and for
+        sequence_bias and bad_words_ids (every window's history starts from that window's prompt, as in HF), the fallback arguments --
+        with top_k / top_p / min_p / seed the ladder samples on the device: a draw is addressed by (seed, recording, history position,
+        seek-loop iteration * MAX_LADDER_RUNGS + rung), so no two of one call share a Philox counter --, and for
         num_beams > 1 length_penalty, early_stopping and reorder_caches (False: beam_search's default beam-indirect caches; True: its
         former copying path).
         Returns per recording a list of segments dict(start, end, tokens) in seconds / token ids."""
@@ -874,11 +1025,15 @@ class LongFormDecoder:
                   **{k: gen_kw.get(k) for k in ("suppress_tokens", "begin_suppress_tokens", "ctc", "repetition_penalty", "no_repeat_ngram_size",
                                                       "sequence_bias", "bad_words_ids")})
         ladder = gen_kw.get("temperatures") is not None and self.num_beams == 1
+        iteration = 0                                              # seek-loop iterations so far: part of the sampler's stream word
         if ladder:
             # temperature fallback (reference generation.py:567-611): per-window ladder, silent windows skipped (skip_by_row=True
             # keeps a silent window's flag with ITS recording; default = transformers' position in the sub-batch, see decode_with_fallback)
             kw.update({k: gen_kw[k] for k in ("temperatures", "compression_ratio_threshold", "logprob_threshold", "no_speech_threshold",
-                                              "no_speech_token_id", "generator", "skip_by_row") if k in gen_kw})
+                                              "no_speech_token_id", "generator", "skip_by_row", "top_k", "top_p", "min_p", "seed") if k in gen_kw})
+            on_device = sampling_options(*(kw.get(k) for k in ("top_k", "top_p", "min_p", "seed")), kw.get("generator")) is not None
+            if on_device and len(kw["temperatures"]) > MAX_LADDER_RUNGS:
+                raise ValueError(f"the device sampler addresses at most {MAX_LADDER_RUNGS} rungs, but the ladder has {len(kw['temperatures'])}")
         elif self.num_beams > 1:
             kw.update(length_penalty=gen_kw.get("length_penalty", 1.0), early_stopping=gen_kw.get("early_stopping", False),
                       reorder_caches=gen_kw.get("reorder_caches", False))
@@ -894,7 +1049,9 @@ class LongFormDecoder:
             enr = None if enrollments is None else {k: v[active] for k, v in enrollments.items()}
             skip = [False] * len(active)
             if ladder:
-                tok_lists, skip, _ = self.decoder.generate_with_fallback(feats, stno, prompt[active], n_new, enrollments=enr, **kw)
+                where = dict(row_ids=active, stream=iteration * MAX_LADDER_RUNGS) if on_device else {}
+                tok_lists, skip, _ = self.decoder.generate_with_fallback(feats, stno, prompt[active], n_new, enrollments=enr, **where, **kw)
+                iteration += 1
             else:
                 if self.num_beams > 1:
                     seqs, _ = self.decoder.beam_search(feats, stno, prompt[active], P + n_new, self.num_beams, enrollments=enr, **kw)

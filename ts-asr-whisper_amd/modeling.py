@@ -775,9 +775,11 @@ class DiCoWForConditionalGeneration(_ModelBase):
         (generation.LongFormDecoder) and the window-relative sequences of _fix_timestamps_from_segmentation.
         ``generation_config``: any object with the HF / reference attribute names (eos_token_id, pad_token_id, suppress_tokens,
         begin_suppress_tokens, return_timestamps, no_timestamps_token_id, max_initial_timestamp_index, ctc_weight,
-        repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, ...).
+        repetition_penalty, no_repeat_ngram_size, sequence_bias, bad_words_ids, top_k, top_p, min_p, seed, ...).
+        top_k / top_p / min_p / seed take effect on the temperature-fallback ladder (``temperature`` a tuple), whose rungs then sample on
+        the device (generation.sample_tokens); greedy and beam decoding do not consult them.
         The prompt is ``decoder_input_ids`` or [decoder_start_token_id] + the tokenizer's prefix tokens."""
-        from .generation import repetition_options, sequence_bias_options
+        from .generation import repetition_options, sampling_options, sequence_bias_options
         gc = generation_config if generation_config is not None else self.generation_config
         # (explicit keyword arguments win over the generation config, as in HF's generate)
         # -- except `temperature`, which HF's WhisperGenerationMixin.generate (the method the reference delegates to) takes from
@@ -825,6 +827,11 @@ class DiCoWForConditionalGeneration(_ModelBase):
         rep_kw.update(sequence_bias=get("sequence_bias"), bad_words_ids=get("bad_words_ids"))
         sequence_bias_options(rep_kw["sequence_bias"], rep_kw["bad_words_ids"], get("eos_token_id", self.config.eos_token_id),
                               self.config.vocab_size)
+        # HF's sampling warpers and the device sampler's seed (generation.sample_tokens): they act on the rungs of the fallback ladder,
+        # the one path that samples; validated here likewise
+        smp_kw = {k: get(k) for k in ("top_k", "top_p", "min_p", "seed")}
+        sampling_options(generator=get("generator"), **smp_kw)
+        rep_kw.update({k: v for k, v in smp_kw.items() if v is not None and ladder and takes_seek_loop})
         if takes_seek_loop:
             if one_window_seek and attention_mask is None:
                 attention_mask = torch.ones(input_features.shape[0], n_frames, dtype=torch.long, device=input_features.device)
